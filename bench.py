@@ -11,9 +11,14 @@ Multi-GPU (launched by torch.distributed.run, one rank per GPU): the batch dimen
 sharded, every rank transforms its own `batch` polynomials, no data-path collective
  — weak scaling.  torch is used for rendezvous/barrier only.
 
-Extra objects on the JSON line: "roofline" (HIP-event time of the pass kernels of one
-transform, measured live; HBM peak 8 TB/s), "cpu_baseline" (the CPU oracle timed on a
-bounded sample on this box's cores; rank 0, N=1 only) and "sizes" (GB/s at 2^20/2^22/2^24).
+A plain run sets up, warms up, times exactly --steps transforms and prints one JSON line.
+--full adds the extra objects, which take runs of their own: "roofline" (HIP-event time of
+the pass kernels of one transform, measured live; HBM peak 8 TB/s), "cpu_baseline" (the CPU
+oracle timed on a bounded sample on this box's cores; rank 0, N=1 only), "sizes" (GB/s at
+2^20/2^22/2^24) and the optional prove / MapReduce legs, printed on a second, enriched line.
+
+--dump-outputs DIR writes what the last timed step left in the batch (see dump_outputs) for
+output-for-output comparison of two builds: the inputs depend only on the arguments.
 """
 import argparse
 import ctypes
@@ -33,7 +38,7 @@ HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 # bit for bit against the CPU oracle at the full 128 x 2^20 size, and the line reports whether it ran with it
 EXPECTED_HEADLINE_PLAN = "strip(R=2^10,C=2^4,E=32)+finalT(R=2^10,C=2^3,E=32)"
 TIMING_PROTOCOL = ("value: wall clock over exactly --steps back-to-back transforms between barrier+synchronize pairs (mean per step, max "
-                   "over ranks); roofline.achieved: HIP events on the ctx stream around the same --steps transforms (no event between passes); pass_ms_profiling_mode: per-pass HIP-event times, mean over 3-10 transforms with every pass bracketed (slower by the event overhead); sizes: mean of 10 after 3 warm-ups; "
+                   "over ranks); the rest with --full only: roofline.achieved: HIP events on the ctx stream around the same --steps transforms (no event between passes); pass_ms_profiling_mode: per-pass HIP-event times, mean over 3-10 transforms with every pass bracketed (slower by the event overhead); sizes: mean of 10 after 3 warm-ups; "
                    "median_ms_of_50_single_launch_timings: SURVEY 8(d) protocol, each transform bracketed by its own HIP events")
 PMC_TRAFFIC = os.path.join(ROOT, "profiles", "pmc_traffic.json")   # written by profiles/summarize_pmc.py --traffic
 
@@ -80,6 +85,22 @@ def time_ntt(pr, d, log_n, batch, steps, warmup):
         pr.ntt_(d, log_n, batch)
     ms = pr.timer_stop()
     return ms / steps
+
+
+DUMP_SAMPLE = 1 << 21        # elements written by --dump-outputs: two float64 files of 16 MB each
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, d, batch, n):
+    """The batch as the caller of ntt_ receives it after the last timed step, as DIR/ntt_out_lo32.npy and DIR/ntt_out_hi32.npy: the
+    low and high 32-bit halves of every u64 field element, each exact in float64, so the comparison is bit for bit.  A batch of more
+    than DUMP_SAMPLE elements is sampled at fixed flat (row-major) indices drawn from DUMP_SEED."""
+    vals = d.download((batch * n,))
+    if vals.size > DUMP_SAMPLE:
+        vals = vals[np.sort(np.random.default_rng(DUMP_SEED).choice(vals.size, DUMP_SAMPLE, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ntt_out_lo32.npy"), (vals & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(out_dir, "ntt_out_hi32.npy"), (vals >> np.uint64(32)).astype(np.float64))
 
 
 def effective_cpus():
@@ -1103,14 +1124,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--batch", type=int, default=128)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-sizes", action="store_true", help="skip the 2^20/2^22/2^24 sweep")
-    ap.add_argument("--no-prove", action="store_true", help="skip the end-to-end prove leg")
+    ap.add_argument("--full", action="store_true", help="also the single-launch median, the roofline, the other sizes, the CPU baseline and the "
+                                                        "optional prove / MapReduce legs (a plain run times the headline transform only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's output to DIR/*.npy (rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-sizes", action="store_true", help="with --full: skip the 2^20/2^22/2^24 sweep")
+    ap.add_argument("--no-prove", action="store_true", help="with --full: skip the end-to-end prove leg")
     ap.add_argument("--sweep", action="store_true", help="tuning aid: time alternative pass plans and exit")
     ap.add_argument("--hash-bench", action="store_true", help="tuning aid: Poseidon / LDE / Merkle stage times and exit")
     ap.add_argument("--prove-bench", action="store_true", help="end-to-end prove time of the build-defined circuit and exit")
     ap.add_argument("--mapreduce", action="store_true", help="map (leaf proofs sharded over ranks) + all-gather timing and exit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.sweep:
         return sweep()
@@ -1163,8 +1189,30 @@ def main():
     ms_per_step = wall * 1e3 / args.steps
     alg_bytes = 16.0 * n * batch
     value = alg_bytes * world / (ms_per_step * 1e-3) / 1e9
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d, batch, n)
 
     out = None
+    if rank == 0:
+        plan = pr.describe_plan(log_n, batch)
+        out = {
+            "metric": "Goldilocks NTT GB/s @ 2^20\u20132^24", "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+            "config": {"workload": f"forward NTT, n=2^{log_n}, batch={batch} per GPU, in place, natural order "
+                                   f"(BASELINE configs[1] wires shape)", "log_n": log_n, "batch_per_gpu": batch,
+                       "plan": plan, "algorithmic_bytes_per_step": alg_bytes,
+                       "plan_is_the_bit_exact_tested_plan": plan == EXPECTED_HEADLINE_PLAN if (log_n, batch) == (20, 128) else None,
+                       "event_ms_per_step": round(ev_ms / args.steps, 4), "timing": TIMING_PROTOCOL},
+        }
+    if not args.full:
+        d.free()
+        pr.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        _finish(world)
+        return
+
     if rank == 0:
         # SURVEY.md 8(d)'s protocol beside the contract's mean: 50 individually HIP-event-timed transforms after the warm-up, median
         singles = []
@@ -1189,25 +1237,15 @@ def main():
         # from the profiling mode, which brackets every pass with its own events and runs ~2 % slower: it apportions, it does not define.
         kern_ms = ev_ms / args.steps
         achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-        out = {
-            "metric": "Goldilocks NTT GB/s @ 2^20\u20132^24", "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "config": {"workload": f"forward NTT, n=2^{log_n}, batch={batch} per GPU, in place, natural order "
-                                   f"(BASELINE configs[1] wires shape)", "log_n": log_n, "batch_per_gpu": batch,
-                       "plan": pr.describe_plan(log_n, batch), "algorithmic_bytes_per_step": alg_bytes,
-                       "plan_is_the_bit_exact_tested_plan": (pr.describe_plan(log_n, batch) == EXPECTED_HEADLINE_PLAN
-                                                             if (log_n, batch) == (20, 128) else None),
-                       "event_ms_per_step": round(ev_ms / args.steps, 4), "median_ms_of_50_single_launch_timings": round(median50, 4),
-                       "median_of_50_gbps": round(alg_bytes / (median50 * 1e-3) / 1e9, 1), "timing": TIMING_PROTOCOL},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "traffic": pmc_traffic_bytes(pr.describe_plan(log_n, batch), float(n) * batch),
-                         "kernel": "glp_ntt_pass_kernel (all passes of one transform)",
-                         "kernel_ms_per_transform": round(kern_ms, 4),
-                         "pass_ms_profiling_mode": [round(m, 4) for m in pass_ms],
-                         "pass_gbps_profiling_mode": [round(alg_bytes / (m * 1e-3) / 1e9, 1) for m in pass_ms]},
-        }
+        out["config"].update({"median_ms_of_50_single_launch_timings": round(median50, 4),
+                              "median_of_50_gbps": round(alg_bytes / (median50 * 1e-3) / 1e9, 1)})
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                           "traffic": pmc_traffic_bytes(plan, float(n) * batch),
+                           "kernel": "glp_ntt_pass_kernel (all passes of one transform)",
+                           "kernel_ms_per_transform": round(kern_ms, 4),
+                           "pass_ms_profiling_mode": [round(m, 4) for m in pass_ms],
+                           "pass_gbps_profiling_mode": [round(alg_bytes / (m * 1e-3) / 1e9, 1) for m in pass_ms]}
     d.free()
 
     if rank == 0 and not args.no_sizes:

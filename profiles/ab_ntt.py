@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 libs = sys.argv[1:]
 rounds = int(os.environ.get("AB_ROUNDS", "3"))
-extra = os.environ.get("AB_ARGS", "--no-cpu --no-sizes --no-prove --steps 30 --warmup 5").split()
+extra = os.environ.get("AB_ARGS", "--full --no-cpu --no-sizes --no-prove --steps 30 --warmup 5").split()
 for r in range(rounds):
     for lib in libs:
         env = dict(os.environ, GLP_LIB=os.path.abspath(lib))
