@@ -1,6 +1,7 @@
 // nnf25519.h — witness arithmetic for the NON-NATIVE field F_q, q = 2^255 - 19 (Curve25519's base field), as the in-circuit Ed25519
 // gadgets use it (0-kno-blobstreamx_amd/ed25519_circuit.py; upstream name recalled: curta's Ed25519
-// chip — reference file:line NONE, the mount is empty).  Host C++ only: this is the straight-line witness evaluator's op 14 (verify.hip).
+// chip — reference file:line NONE, the mount is empty).  Host and device C++ (GL_HD, like gl_field.cuh): this is op 14 of the straight-line witness
+// evaluator, on the host (verify.hip) and in the level-scheduled device kernel (witness_kernels.cuh).
 //
 // Representation: 11 limbs of 24 bits, little endian (264 bits).  A product a * b = k * q + r is shown IN THE CIRCUIT over the integers, column by
 // column of the limb convolution, with carries:
@@ -11,6 +12,13 @@
 // the bounds and refuses products whose columns could leave the carry range.
 #pragma once
 #include <stdint.h>
+#ifndef GL_HD   // the qualifier of gl_field.cuh, for a translation unit that includes this header alone
+#if defined(__HIPCC__)
+#define GL_HD __host__ __device__ __forceinline__
+#else
+#define GL_HD inline __attribute__((always_inline))
+#endif
+#endif
 
 #define GLP_NNF_LIMBS 11
 #define GLP_NNF_BITS 24
@@ -25,8 +33,8 @@ static const uint64_t GOLDILOCKS_P = 0xFFFFFFFF00000001ULL;
 
 // little-endian multi-word unsigned integers, 10 x 64 bits (640 bits: products of two 272-bit values fit)
 struct Big { uint64_t w[10]; };
-static inline Big big_zero() { Big z; for (int i = 0; i < 10; i++) z.w[i] = 0; return z; }
-static inline void big_add_shifted(Big& z, u128 v, unsigned bit) {          // z += v << bit
+GL_HD Big big_zero() { Big z; for (int i = 0; i < 10; i++) z.w[i] = 0; return z; }
+GL_HD void big_add_shifted(Big& z, u128 v, unsigned bit) {          // z += v << bit
     unsigned word = bit >> 6, sh = bit & 63;
     uint64_t parts[3] = {(uint64_t)v, (uint64_t)(v >> 64), 0};
     if (sh) { parts[2] = parts[1] >> (64 - sh); parts[1] = (parts[1] << sh) | (parts[0] >> (64 - sh)); parts[0] <<= sh; }
@@ -38,14 +46,14 @@ static inline void big_add_shifted(Big& z, u128 v, unsigned bit) {          // z
         carry = (unsigned)(s >> 64);
     }
 }
-static inline bool big_is_zero_from(const Big& z, unsigned bit) {           // z >> bit == 0
+GL_HD bool big_is_zero_from(const Big& z, unsigned bit) {           // z >> bit == 0
     unsigned word = bit >> 6, sh = bit & 63;
     if (word >= 10) return true;
     if (z.w[word] >> sh) return false;
     for (unsigned i = word + 1; i < 10; i++) if (z.w[i]) return false;
     return true;
 }
-static inline Big big_shr(const Big& z, unsigned bit) {
+GL_HD Big big_shr(const Big& z, unsigned bit) {
     Big r = big_zero();
     unsigned word = bit >> 6, sh = bit & 63;
     for (unsigned i = 0; i + word < 10; i++) {
@@ -55,32 +63,32 @@ static inline Big big_shr(const Big& z, unsigned bit) {
     }
     return r;
 }
-static inline Big big_low(const Big& z, unsigned bits) {                    // z mod 2^bits
+GL_HD Big big_low(const Big& z, unsigned bits) {                    // z mod 2^bits
     Big r = z;
     unsigned word = bits >> 6, sh = bits & 63;
     if (word < 10) { if (sh) r.w[word] &= ((1ULL << sh) - 1); else r.w[word] = 0; for (unsigned i = word + 1; i < 10; i++) r.w[i] = 0; }
     return r;
 }
-static inline Big big_add(const Big& a, const Big& b) {
+GL_HD Big big_add(const Big& a, const Big& b) {
     Big r; unsigned carry = 0;
     for (int i = 0; i < 10; i++) { u128 s = (u128)a.w[i] + b.w[i] + carry; r.w[i] = (uint64_t)s; carry = (unsigned)(s >> 64); }
     return r;
 }
-static inline Big big_mul_small(const Big& a, uint64_t m) {
+GL_HD Big big_mul_small(const Big& a, uint64_t m) {
     Big r; uint64_t carry = 0;
     for (int i = 0; i < 10; i++) { u128 s = (u128)a.w[i] * m + carry; r.w[i] = (uint64_t)s; carry = (uint64_t)(s >> 64); }
     return r;
 }
-static inline int big_cmp(const Big& a, const Big& b) {
+GL_HD int big_cmp(const Big& a, const Big& b) {
     for (int i = 9; i >= 0; i--) { if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1; }
     return 0;
 }
-static inline Big big_sub(const Big& a, const Big& b) {                     // a >= b
+GL_HD Big big_sub(const Big& a, const Big& b) {                     // a >= b
     Big r; unsigned borrow = 0;
     for (int i = 0; i < 10; i++) { u128 d = (u128)a.w[i] - b.w[i] - borrow; r.w[i] = (uint64_t)d; borrow = (unsigned)((d >> 64) & 1); }
     return r;
 }
-static inline uint64_t big_limb(const Big& z, unsigned idx) {               // 24-bit limb idx
+GL_HD uint64_t big_limb(const Big& z, unsigned idx) {               // 24-bit limb idx
     unsigned bit = idx * GLP_NNF_BITS, word = bit >> 6, sh = bit & 63;
     if (word >= 10) return 0;
     uint64_t v = z.w[word] >> sh;
@@ -91,7 +99,7 @@ static inline uint64_t big_limb(const Big& z, unsigned idx) {               // 2
 // out[0..11) = r limbs, out[11..23) = k limbs, out[23..44) = carries c_0..c_20 as Goldilocks elements (negative c -> p - |c|).
 // a, b: limb values (any u64 below 2^28; the circuit's own bound tracking is stricter).  Returns false when an operand limb is out of range or
 // the carries leave +-2^62 (cannot happen for in-range operands).
-static inline bool mul_hints(const uint64_t* a, const uint64_t* b, uint64_t* out) {
+GL_HD bool mul_hints(const uint64_t* a, const uint64_t* b, uint64_t* out) {
     for (int i = 0; i < GLP_NNF_LIMBS; i++) if ((a[i] >> 28) || (b[i] >> 28)) return false;
     u128 ab[GLP_NNF_COLS];
     for (int t = 0; t < GLP_NNF_COLS; t++) ab[t] = 0;

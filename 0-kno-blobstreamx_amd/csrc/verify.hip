@@ -23,6 +23,7 @@
 #include "challenger.h"
 #include "plonk_gates.h"
 #include "nnf25519.h"
+#include "witness_plan.h"
 
 namespace {
 const u64 FRI_TAG = 0x32304952464C4747ull;
@@ -620,8 +621,10 @@ extern "C" int glp_poseidon_permute_host(const uint64_t* h_rc, const uint64_t* h
 
 // ---- witness evaluator for circuits recorded by the host builder (recursion.py::WitnessProgram) -------------------------------------
 // A recorded circuit is a straight-line program over its variables: arithmetic gates, free inputs, bit extractions, inverses, Poseidon
-// permutations — each op defines NEW variables from earlier ones, so one forward pass computes the whole witness.  The dependency chain is
-// sequential (host work by nature, like the transcript); different proofs/circuits evaluate independently.  Program words (u64):
+// permutations — each op defines NEW variables from earlier ones, so one forward pass computes the whole witness.  This file walks the ops
+// one after the other on the host (segments on several threads: glp_witness_eval_mt).  The dependency chain is far shorter than the program —
+// a signature leaf is 1.2 M ops in 8 k dependency levels — which is what the batched device evaluator uses (witness_plan.h compiles the level
+// schedule, witness_kernels.cuh runs it: glp_witness_eval_device); both decode with one table of op lengths (GLP_WIT_OP_LEN).  Program words (u64):
 //   0 ARITH  w x y z c0 c1 c2   w = c0*x*y + c1*z + c2        1 INPUT w i          w = inputs[i]
 //   2 BIT    w x k              w = bit k of canonical x        3 INV   w x          w = 1/x (0 -> 0)
 //   4 EINV   w0 w1 x0 x1        (w0,w1) = 1/(x0 + x1 X)          5 ZERO  w            w = 0
@@ -658,52 +661,52 @@ static int witness_run(const Hasher& h, const u64* prog, size_t pc, size_t end, 
         const u64* a = prog + pc + 1;
         switch (op) {
             case 0: {
-                if (pc + 8 > end || !ok(a[0]) || !ok(a[1]) || !ok(a[2]) || !ok(a[3]) || a[4] >= GL_P || a[5] >= GL_P || a[6] >= GL_P) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[0] > end || !ok(a[0]) || !ok(a[1]) || !ok(a[2]) || !ok(a[3]) || a[4] >= GL_P || a[5] >= GL_P || a[6] >= GL_P) return GLP_E_INVALID;
                 if (!rd(a[1]) || !rd(a[2]) || !rd(a[3]) || !wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = gl_add(gl_add(gl_mul(a[4], gl_mul(values[a[1]], values[a[2]])), gl_mul(a[5], values[a[3]])), a[6]);
-                pc += 8;
+                pc += GLP_WIT_OP_LEN[0];
                 break;
             }
             case 1:
-                if (pc + 3 > end || !ok(a[0]) || a[1] >= n_inputs || inputs[a[1]] >= GL_P || !wr(a[0])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[1] > end || !ok(a[0]) || a[1] >= n_inputs || inputs[a[1]] >= GL_P || !wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = inputs[a[1]];
-                pc += 3;
+                pc += GLP_WIT_OP_LEN[1];
                 break;
             case 2:
-                if (pc + 4 > end || !ok(a[0]) || !ok(a[1]) || a[2] >= 64 || !rd(a[1]) || !wr(a[0])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[2] > end || !ok(a[0]) || !ok(a[1]) || a[2] >= 64 || !rd(a[1]) || !wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = (values[a[1]] >> a[2]) & 1ull;
-                pc += 4;
+                pc += GLP_WIT_OP_LEN[2];
                 break;
             case 3:
-                if (pc + 3 > end || !ok(a[0]) || !ok(a[1]) || !rd(a[1]) || !wr(a[0])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[3] > end || !ok(a[0]) || !ok(a[1]) || !rd(a[1]) || !wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = values[a[1]] ? gl_inv(values[a[1]]) : 0;
-                pc += 3;
+                pc += GLP_WIT_OP_LEN[3];
                 break;
             case 4: {
-                if (pc + 5 > end || !ok(a[0]) || !ok(a[1]) || !ok(a[2]) || !ok(a[3]) || !rd(a[2]) || !rd(a[3]) || !wr(a[0]) || !wr(a[1])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[4] > end || !ok(a[0]) || !ok(a[1]) || !ok(a[2]) || !ok(a[3]) || !rd(a[2]) || !rd(a[3]) || !wr(a[0]) || !wr(a[1])) return GLP_E_INVALID;
                 const gl_ext2 x{values[a[2]], values[a[3]]};
                 const gl_ext2 r = (x.a || x.b) ? ext_inv(x) : gl_ext2{0, 0};
                 values[a[0]] = r.a; values[a[1]] = r.b;
-                pc += 5;
+                pc += GLP_WIT_OP_LEN[4];
                 break;
             }
             case 5:
-                if (pc + 2 > end || !ok(a[0]) || !wr(a[0])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[5] > end || !ok(a[0]) || !wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = 0;
-                pc += 2;
+                pc += GLP_WIT_OP_LEN[5];
                 break;
             case 6: {
-                if (pc + 25 > end) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[6] > end) return GLP_E_INVALID;
                 u64 st[12];
                 for (int i = 0; i < 12; i++) { if (!ok(a[i]) || !ok(a[12 + i]) || !rd(a[12 + i])) return GLP_E_INVALID; st[i] = values[a[12 + i]]; }
                 h.permute(st);
                 for (int i = 0; i < 12; i++) { if (!wr(a[i])) return GLP_E_INVALID; values[a[i]] = st[i]; }
-                pc += 25;
+                pc += GLP_WIT_OP_LEN[6];
                 break;
             }
             // SHA-256 rows (plonk_gates.h): every input must be a 32-bit word (T1: < 2^35) — anything else cannot satisfy the row
             case 7: {   // SHA_E  T1 e_new | e f g h d w | K
-                if (pc + 10 > end || a[8] > 0xFFFFFFFFull) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[7] > end || a[8] > 0xFFFFFFFFull) return GLP_E_INVALID;
                 for (int i = 0; i < 8; i++) if (!ok(a[i])) return GLP_E_INVALID;
                 for (int i = 2; i < 8; i++) if (!rd(a[i])) return GLP_E_INVALID;
                 u64 v[6];
@@ -712,42 +715,42 @@ static int witness_run(const Hasher& h, const u64* prog, size_t pc, size_t end, 
                 const u64 t1 = v[3] + glp_sha_S1(v[0]) + glp_sha_ch(v[0], v[1], v[2]) + a[8] + v[5];
                 values[a[0]] = t1;
                 values[a[1]] = (v[4] + t1) & 0xFFFFFFFFull;
-                pc += 10;
+                pc += GLP_WIT_OP_LEN[7];
                 break;
             }
             case 8: {   // SHA_A  a_new | a b c T1
-                if (pc + 6 > end) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[8] > end) return GLP_E_INVALID;
                 for (int i = 0; i < 5; i++) if (!ok(a[i])) return GLP_E_INVALID;
                 for (int i = 1; i < 5; i++) if (!rd(a[i])) return GLP_E_INVALID;
                 const u64 va = values[a[1]], vb = values[a[2]], vc = values[a[3]], t1 = values[a[4]];
                 if ((va | vb | vc) >> 32 || t1 >> 35) return GLP_E_REJECT;
                 if (!wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = (t1 + glp_sha_S0(va) + glp_sha_maj(va, vb, vc)) & 0xFFFFFFFFull;
-                pc += 6;
+                pc += GLP_WIT_OP_LEN[8];
                 break;
             }
             case 9: {   // SHA_W  w_new | w16 w15 w7 w2
-                if (pc + 6 > end) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[9] > end) return GLP_E_INVALID;
                 for (int i = 0; i < 5; i++) if (!ok(a[i])) return GLP_E_INVALID;
                 for (int i = 1; i < 5; i++) if (!rd(a[i])) return GLP_E_INVALID;
                 const u64 w16 = values[a[1]], w15 = values[a[2]], w7 = values[a[3]], w2 = values[a[4]];
                 if ((w16 | w15 | w7 | w2) >> 32) return GLP_E_REJECT;
                 if (!wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = (w16 + glp_sha_s0(w15) + w7 + glp_sha_s1(w2)) & 0xFFFFFFFFull;
-                pc += 6;
+                pc += GLP_WIT_OP_LEN[9];
                 break;
             }
             case 10: {  // ADD32  s | x y
-                if (pc + 4 > end || !ok(a[0]) || !ok(a[1]) || !ok(a[2]) || !rd(a[1]) || !rd(a[2])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[10] > end || !ok(a[0]) || !ok(a[1]) || !ok(a[2]) || !rd(a[1]) || !rd(a[2])) return GLP_E_INVALID;
                 const u64 x = values[a[1]], y = values[a[2]];
                 if ((x | y) >> 32) return GLP_E_REJECT;
                 if (!wr(a[0])) return GLP_E_INVALID;
                 values[a[0]] = (x + y) & 0xFFFFFFFFull;
-                pc += 4;
+                pc += GLP_WIT_OP_LEN[10];
                 break;
             }
             case 12: {  // POSEIDON_SWAP o0..o11 | i0..i11 | s:  the permutation of the input with its first two 4-word blocks exchanged when s = 1
-                if (pc + 26 > end || !ok(a[24]) || !rd(a[24])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[12] > end || !ok(a[24]) || !rd(a[24])) return GLP_E_INVALID;
                 u64 st[12];
                 for (int i = 0; i < 12; i++) { if (!ok(a[i]) || !ok(a[12 + i]) || !rd(a[12 + i])) return GLP_E_INVALID; st[i] = values[a[12 + i]]; }
                 const u64 sw = values[a[24]];
@@ -755,22 +758,22 @@ static int witness_run(const Hasher& h, const u64* prog, size_t pc, size_t end, 
                 if (sw) for (int i = 0; i < 4; i++) { const u64 t = st[i]; st[i] = st[4 + i]; st[4 + i] = t; }
                 h.permute(st);
                 for (int i = 0; i < 12; i++) { if (!wr(a[i])) return GLP_E_INVALID; values[a[i]] = st[i]; }
-                pc += 26;
+                pc += GLP_WIT_OP_LEN[12];
                 break;
             }
             case 13: {  // EXTMULADD  w0 w1 | x0 x1 y0 y1 z0 z1:  w = x * y + z in F_p[X]/(X^2 - 7)
-                if (pc + 9 > end) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[13] > end) return GLP_E_INVALID;
                 for (int i = 0; i < 8; i++) if (!ok(a[i])) return GLP_E_INVALID;
                 for (int i = 2; i < 8; i++) if (!rd(a[i])) return GLP_E_INVALID;
                 const gl_ext2 x{values[a[2]], values[a[3]]}, y{values[a[4]], values[a[5]]}, z{values[a[6]], values[a[7]]};
                 const gl_ext2 w = gl_ext_add(gl_ext_mul(x, y), z);
                 if (!wr(a[0]) || !wr(a[1])) return GLP_E_INVALID;
                 values[a[0]] = w.a; values[a[1]] = w.b;
-                pc += 9;
+                pc += GLP_WIT_OP_LEN[13];
                 break;
             }
             case 14: {  // NNF_MUL  first | a0..a10 | b0..b10:  the 44 hint values of a product in F_q, q = 2^255 - 19 (nnf25519.h): r, k, carries
-                if (pc + 2 + 2 * GLP_NNF_LIMBS > end || a[0] >= n_values || a[0] + GLP_NNF_OUT > n_values) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[14] > end || a[0] >= n_values || a[0] + GLP_NNF_OUT > n_values) return GLP_E_INVALID;
                 u64 va[GLP_NNF_LIMBS], vb[GLP_NNF_LIMBS], out[GLP_NNF_OUT];
                 for (int i = 0; i < GLP_NNF_LIMBS; i++) {
                     const u64 ia = a[1 + i], ib = a[1 + GLP_NNF_LIMBS + i];
@@ -779,14 +782,14 @@ static int witness_run(const Hasher& h, const u64* prog, size_t pc, size_t end, 
                 }
                 if (!glp_nnf::mul_hints(va, vb, out)) return GLP_E_REJECT;         // an operand limb out of range: no witness satisfies the product rows
                 for (int i = 0; i < GLP_NNF_OUT; i++) { if (!wr(a[0] + i)) return GLP_E_INVALID; values[a[0] + i] = out[i]; }
-                pc += 2 + 2 * GLP_NNF_LIMBS;
+                pc += GLP_WIT_OP_LEN[14];
                 break;
             }
             case 11: {  // BITS  w | x shift bits:  w = (x >> shift) mod 2^bits
-                if (pc + 5 > end || !ok(a[0]) || !ok(a[1]) || a[2] >= 64 || a[3] == 0 || a[3] > 64 || !rd(a[1]) || !wr(a[0])) return GLP_E_INVALID;
+                if (pc + GLP_WIT_OP_LEN[11] > end || !ok(a[0]) || !ok(a[1]) || a[2] >= 64 || a[3] == 0 || a[3] > 64 || !rd(a[1]) || !wr(a[0])) return GLP_E_INVALID;
                 const u64 sh = values[a[1]] >> a[2];
                 values[a[0]] = a[3] >= 64 ? sh : (sh & ((1ull << a[3]) - 1));
-                pc += 5;
+                pc += GLP_WIT_OP_LEN[11];
                 break;
             }
             default: return GLP_E_INVALID;

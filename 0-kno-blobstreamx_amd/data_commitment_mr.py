@@ -88,9 +88,12 @@ class DataCommitmentMapReduce:
         """routed wires of the circuits a level-`level` node verifies (80 of 144 everywhere here)"""
         return 80
 
-    def __init__(self, prover, poseidon_consts, leaf_blocks=64, fan_in=8, num_queries=28, pow_bits=16, map_provers=()):
+    def __init__(self, prover, poseidon_consts, leaf_blocks=64, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
+                 device_witness_chunk=32):
         """map_provers: further Provers on the same GPU (their Poseidon constants set): the Map step then proves leaves on all of them at once,
-        one host thread each (the latency-bound phases of one leaf proof overlap the throughput-bound phases of another, as in mapreduce.py)"""
+        one host thread each (the latency-bound phases of one leaf proof overlap the throughput-bound phases of another, as in mapreduce.py).
+        device_witness (default off: the host evaluator pool): the Map step evaluates the leaves' witness programs ON THE DEVICE, device_witness_chunk
+        leaves per launch (WitnessProgram.evaluate_device; 32 signature leaves are a 340 MB slab), and the provers place and prove from the slab."""
         assert leaf_blocks >= 1 and leaf_blocks & (leaf_blocks - 1) == 0 and fan_in >= 2 and fan_in & (fan_in - 1) == 0
         self.prover, self.consts = prover, tuple(np.ascontiguousarray(a, dtype=np.uint64) for a in poseidon_consts)
         self.map_provers, self.map_circuits = list(map_provers), []
@@ -99,6 +102,7 @@ class DataCommitmentMapReduce:
         self.nodes = {}                 # (level, fan-in, span, child key) -> RecursionProgram
         self.node_replicas = {}         # id(node program) -> [its replicas on each map prover]
         self.record_seconds = {}
+        self.device_witness, self.device_witness_chunk = bool(device_witness), max(1, int(device_witness_chunk))
 
     # ---- Map ----------------------------------------------------------------------------------------------------------------------
     def _record_leaf(self):
@@ -138,6 +142,8 @@ class DataCommitmentMapReduce:
         first ones.  A witness that does not satisfy the circuit raises ValueError from here."""
         import os
         from concurrent.futures import ThreadPoolExecutor
+        if getattr(self, "device_witness", False):
+            return self._map_inputs_device(inputs_list)
         n_workers = 1 + len(self.map_provers)
         n_eval = max(1, min(len(inputs_list), (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count() or 2) - n_workers, 12))
         evaluate = lambda inp: self.leaf_program.evaluate(self.consts, inp, threads=1)
@@ -163,6 +169,49 @@ class DataCommitmentMapReduce:
                 for f in futs:
                     f.cancel()
         return [p for _, p in done]
+
+    def _map_inputs_device(self, inputs_list):
+        """_map_inputs with the witness programs evaluated on the device: chunks of device_witness_chunk input vectors on the main prover's
+        stream (glp_witness_eval_device returns with the stream synchronised, so the map provers' streams may read the slab), then every prover
+        places and proves its share of the chunk from the slab — no evaluator pool, no host copy of the variables.  A refused witness raises
+        ValueError naming its position in inputs_list."""
+        from concurrent.futures import ThreadPoolExecutor
+        n_workers = 1 + len(self.map_provers)
+        chunk = self.device_witness_chunk
+        out, slab = [None] * len(inputs_list), None
+        pool = ThreadPoolExecutor(n_workers - 1) if n_workers > 1 and len(inputs_list) > 1 else None
+        try:
+            for lo in range(0, len(inputs_list), chunk):
+                part = inputs_list[lo:lo + chunk]
+                try:
+                    slab = self.leaf_program.evaluate_device(self.prover, part, slab=slab)
+                except ValueError as e:
+                    msg = str(e)
+                    if msg.startswith("instance "):
+                        k, rest = msg[len("instance "):].split(":", 1)
+                        msg = f"instance {lo + int(k)}:{rest}"
+                    raise ValueError(msg) from None
+
+                def work(w, lo=lo, part=part, slab=slab):
+                    if w:
+                        self.map_provers[w - 1].bind_thread()
+                    prover, circuit = (self.prover, self.leaf_circuit) if w == 0 else (self.map_provers[w - 1], self.map_circuits[w - 1])
+                    for i in range(w, len(part), n_workers):
+                        dw, public = slab.device_witness(prover, i, reuse=True)
+                        out[lo + i] = circuit.prove_(dw, self.nq, self.pw, public=public)
+                if pool is None:
+                    work(0)
+                else:
+                    futs = [pool.submit(work, w) for w in range(1, n_workers)]
+                    work(0)
+                    for f in futs:
+                        f.result()
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True)
+            if slab is not None:
+                slab.free()
+        return out
 
     def prove_leaves(self, heights, data_roots):
         """the Map step of a (sub)range: its leaf proofs in order, on every prover this object has"""
@@ -405,13 +454,14 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
     N_PUBLIC = 25
 
     def __init__(self, prover, poseidon_consts, leaf_headers=8, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), height_varint_bytes=4,
-                 field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), defer_commitment=None):
+                 field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), defer_commitment=None, device_witness=False,
+                 device_witness_chunk=32):
         """defer_commitment (default: leaves of 8 or more headers): the leaves expose their headers' data hashes and the LEVEL-1 NODES hash the
         (height, data_hash) tuples and the leaf subtrees — round 3: an 8-header leaf is 368 compressions x 178 rows = 2.7k rows past 2^16; without
         its 30 tuple / subtree compressions it fits 2^16 rows (half the leaf proof), and the node circuit (75k of 131k rows used) has the room.
         The statement of every node — hence of the root — is unchanged; a chain of ONE leaf has no node and is refused in this mode."""
         super().__init__(prover, poseidon_consts, leaf_blocks=leaf_headers, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
-                         map_provers=map_provers)
+                         map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk)
         self.defer = (leaf_headers >= 8) if defer_commitment is None else bool(defer_commitment)
         if self.defer and leaf_headers & (leaf_headers - 1):
             raise ValueError("deferred tuple hashing needs a power-of-two number of headers per leaf")

@@ -518,6 +518,80 @@ class CircuitBuilder:
         return ck, dw, public
 
 
+class DeviceWitnessBatch:
+    """The variables of B instances of one recorded circuit, resident on one prover's device: rows of n_values + len(fixed_values) words (the
+    constants of unused gate slots are written once per row, when the slab is made).  From WitnessProgram.evaluate_device."""
+
+    def __init__(self, program, prover, rows):
+        self.program, self.prover, self.rows, self.B = program, prover, int(rows), 0
+        self.stride = program.n_values + program.fixed_values.size
+        self.buf = DeviceBuffer(prover, max(8, self.rows * self.stride * 8))
+        self.d_in = None
+        nf = program.fixed_values.size
+        if nf and self.rows:
+            fv = np.ascontiguousarray(program.fixed_values, dtype=np.uint64)         # the fixed tail of every row (a few words; no host image of the slab)
+            for i in range(self.rows):
+                prover._chk(prover.lib.glp_h2d(prover.ctx, self.buf.ptr + (i * self.stride + program.n_values) * 8, fv.ctypes.data, fv.nbytes), "glp_h2d")
+
+    def row_ptr(self, i):
+        if not 0 <= i < self.B:
+            raise IndexError("no such instance in this batch")
+        return self.buf.ptr + i * self.stride * 8
+
+    def gather_vars(self, i, var_index):
+        """values of the given variables of instance i: one small device gather + download (not a download of the row)"""
+        idx = np.ascontiguousarray(var_index, dtype=np.uint32)
+        if idx.size == 0:
+            return np.zeros(0, dtype=np.uint64)
+        d_idx = self.prover.to_device(idx)
+        d_out = DeviceBuffer(self.prover, idx.size * 8)
+        try:
+            self.prover.gather(d_out, self.row_ptr(i), self.stride, d_idx, idx.size)
+            return d_out.download(idx.size)
+        finally:
+            d_idx.free()
+            d_out.free()
+
+    def device_witness(self, prover, i, reuse=True):
+        """placement + row fillers from slab row i, NO host copy of the variables: (wire buffer, public values) like WitnessProgram.device_witness.
+        prover: this batch's prover or another ctx on the same device (the map provers of one GPU) — the caller orders the streams: evaluate_device
+        has synchronised its stream before it returned."""
+        prog = self.program
+        n = 1 << prog.log_n
+        r = prog._resident(prover)
+        if reuse:
+            if r["wires"] is None or r["wires"].ptr is None:
+                r["wires"] = DeviceBuffer(prover, prog.W * n * 8)
+            dw = r["wires"]
+        else:
+            dw = DeviceBuffer(prover, prog.W * n * 8)
+        prover.gather(dw, self.row_ptr(i), self.stride, r["cell"], prog.W * n)
+        if r["pos"] is not None:
+            prover._chk(prover.lib.glp_poseidon_gate_fill_rows(prover.ctx, dw.ptr, prog.log_n, prog.W, r["pos"].ptr, prog.pos_row_ids.size),
+                        "glp_poseidon_gate_fill_rows")
+        if r["sha"] is not None:
+            prover._chk(prover.lib.glp_sha_gate_fill_rows(prover.ctx, dw.ptr, prog.log_n, prog.W, r["sha"].ptr, r["kinds"].ptr, prog.sha_row_ids.size),
+                        "glp_sha_gate_fill_rows")
+        if "pub_idx" not in r:
+            r["pub_idx"] = prover.to_device(prog.public_vars.astype(np.uint32)) if prog.public_vars.size else None
+            r["pub_out"] = DeviceBuffer(prover, max(8, prog.public_vars.size * 8))
+        public = []
+        if prog.public_vars.size:
+            prover.gather(r["pub_out"], self.row_ptr(i), self.stride, r["pub_idx"], prog.public_vars.size)
+            public = [int(v) for v in r["pub_out"].download(prog.public_vars.size)]
+        return dw, public
+
+    def download(self, i):
+        """the variables of instance i on the host (tests, debugging)"""
+        self.row_ptr(i)
+        return self.buf.download(self.program.n_values, offset_bytes=i * self.stride * 8)
+
+    def free(self):
+        for b in (self.buf, self.d_in):
+            if b is not None and b.ptr is not None and getattr(b.prover, "ctx", None):
+                b.free()
+
+
 class WitnessProgram:
     """A circuit recorded by CircuitBuilder, separated from the witness it was recorded with: the layout (which variable sits in which cell,
     the constant columns, sigma) and the program that recomputes every variable from the free inputs.  `setup` commits the circuit once;
@@ -752,6 +826,71 @@ class WitnessProgram:
         if rcode != 0:
             raise ValueError("witness program or inputs malformed")
         return vals
+
+    def plan(self):
+        """the program compiled into a level schedule (glp_witness_plan_create; cached, not part of save / load: rebuilt on demand).  Host work,
+        no GPU.  The plan — and the copy of it a device holds after the first evaluate_device there — lives as long as this object."""
+        import ctypes
+        import weakref
+        pl = self.__dict__.get("_plan")
+        if pl is None:
+            from . import load_library
+            lib = load_library()
+            h = ctypes.c_void_p()
+            rc = lib.glp_witness_plan_create(self.prog.ctypes.data, self.prog.size, self.n_inputs, self.n_values,
+                                             self.eq_pairs.ctypes.data if self.eq_pairs.size else None, self.eq_pairs.size // 2, ctypes.byref(h))
+            if rc != 0:
+                raise ValueError("witness program malformed" if rc == -1 else f"glp_witness_plan_create: {rc}")
+            pl = self._plan = h.value
+            self._plan_finalizer = weakref.finalize(self, lib.glp_witness_plan_destroy, ctypes.c_void_p(pl))
+            self._plan_finalizer.atexit = False          # at interpreter exit the driver frees the device copy; the HIP runtime may be gone by then
+        return pl
+
+    def plan_stats(self):
+        """{'ops', 'depth', 'steps', 'stream_bytes'} of the level schedule: steps = barrier-separated passes of the kernel's workgroup"""
+        import ctypes
+        from . import load_library
+        v = [ctypes.c_uint64() for _ in range(4)]
+        rc = load_library().glp_witness_plan_stats(self.plan(), *(ctypes.byref(x) for x in v))
+        if rc != 0:
+            raise ValueError(f"glp_witness_plan_stats: {rc}")
+        return dict(zip(("ops", "depth", "steps", "stream_bytes"), (int(x.value) for x in v)))
+
+    def evaluate_device(self, prover, inputs_batch, slab=None):
+        """every variable of B input vectors computed ON THE DEVICE (glp_witness_eval_device: one workgroup per instance, level by level):
+        returns a DeviceWitnessBatch owning the [B][n_values + fixed] slab.  ValueError with evaluate's texts (naming the instance) when an
+        instance is refused.  slab: a DeviceWitnessBatch of an earlier call to reuse (same prover, at least as many rows)."""
+        import ctypes
+        inp = np.ascontiguousarray(inputs_batch, dtype=np.uint64)
+        if inp.ndim == 1:
+            inp = inp.reshape(1, -1)
+        if inp.ndim != 2 or inp.shape[1] != self.n_inputs:
+            raise ValueError(f"{inp.shape[-1] if inp.ndim else 0} inputs given, the program takes {self.n_inputs}")
+        B = inp.shape[0]
+        plan = self.plan()
+        if slab is None or slab.prover is not prover or slab.rows < B or slab.program is not self or slab.buf.ptr is None:
+            slab = DeviceWitnessBatch(self, prover, B)
+        slab.B = B
+        if B == 0:
+            return slab
+        need = max(8, inp.nbytes)
+        if slab.d_in is None or slab.d_in.ptr is None or slab.d_in.nbytes < need:
+            if slab.d_in is not None and slab.d_in.ptr is not None:
+                slab.d_in.free()
+            slab.d_in = DeviceBuffer(prover, need)
+        if inp.size:
+            slab.d_in.upload(inp)
+        status = np.zeros(B, dtype=np.int32)
+        bad = np.zeros(B, dtype=np.uint64)
+        prover._chk(prover.lib.glp_witness_eval_device(prover.ctx, plan, slab.d_in.ptr, slab.buf.ptr, slab.stride, B, status.ctypes.data, bad.ctypes.data),
+                    "glp_witness_eval_device")
+        for i in np.nonzero(status)[0].tolist():
+            if status[i] == -7:
+                what = ("a row input is out of range (a SHA word above 32 bits, a swap bit above 1)" if int(bad[i]) == 0xFFFFFFFFFFFFFFFF
+                        else f"copy constraint {int(bad[i])} fails")
+                raise ValueError(f"instance {i}: the inputs do not satisfy the circuit ({what})")
+            raise ValueError(f"instance {i}: witness program or inputs malformed")
+        return slab
 
     def inputs_from_words(self, word_lists):
         """the input vector of a program whose inputs were tagged (list number, word position) — e.g. the proofs a verifier circuit consumes —

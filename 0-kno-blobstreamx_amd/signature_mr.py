@@ -32,10 +32,12 @@ LEAF_PUBLIC = 17
 class SignatureSetMapReduce(DataCommitmentMapReduce):
     N_PUBLIC = 12                                   # nodes: block hash (8), signer-digest subtree (4)
 
-    def __init__(self, prover, poseidon_consts, msg_len=112, hash_offset=16, fan_in=8, num_queries=28, pow_bits=16, map_provers=()):
+    def __init__(self, prover, poseidon_consts, msg_len=112, hash_offset=16, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
+                 device_witness_chunk=32):
         if hash_offset + 32 > msg_len or hash_offset % 4 or msg_len % 4:
             raise ValueError("the vote bytes must hold a 32-byte block hash at a word-aligned offset")
-        super().__init__(prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits, map_provers=map_provers)
+        super().__init__(prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits, map_provers=map_provers,
+                         device_witness=device_witness, device_witness_chunk=device_witness_chunk)
         self.msg_len, self.hash_offset = int(msg_len), int(hash_offset)
 
     def _child_n_public(self, level):

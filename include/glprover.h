@@ -306,7 +306,8 @@ int glp_plonk_proof_digest(glp_ctx* ctx, const uint8_t* h_proof, size_t proof_le
 /* Witness evaluator for circuits recorded by the host builder (0-kno-blobstreamx_amd/recursion.py::WitnessProgram): a straight-line program
  * (arithmetic gates, inputs, bit extractions, inverses, Poseidon permutations; encoding in csrc/verify.hip) computes every variable of the circuit
  * from its inputs in one forward pass, then the copy constraints between different variables (eq_pairs, 2 indices each) are checked:
- * GLP_E_REJECT + *first_bad when the witness does not satisfy the circuit.  Host arithmetic: the chain is sequential, like the transcript. */
+ * GLP_E_REJECT + *first_bad when the witness does not satisfy the circuit.  Host arithmetic, one op after the other (the batched device form:
+ * glp_witness_eval_device below). */
 int glp_witness_eval(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint64_t* prog, size_t prog_words,
                      const uint64_t* inputs, size_t n_inputs, uint64_t* values, size_t n_values, const uint64_t* eq_pairs, size_t n_eq,
                      size_t* first_bad);
@@ -321,6 +322,31 @@ int glp_witness_eval_mt(const uint64_t* h_rc, const uint64_t* h_mds_circ, const 
  * — checked on the device: an out-of-range entry writes 0 and the call returns GLP_E_INVALID).  With d_index = the circuit's cell -> variable map
  * (resident, built once per circuit) and d_src = the evaluated variables, this lays out the wire matrix without a host-side copy of it. */
 int glp_gather_u64(glp_ctx* ctx, uint64_t* d_dst, const uint64_t* d_src, size_t n_src, const uint32_t* d_index, size_t n);
+/* Device-side witness evaluation.  A PLAN is the witness program compiled once into a level schedule (level of an op = 1 + the highest level
+ * among the producers of its operands; ops without operands are level 0): ops ordered by (level, kind), 32-bit variable indices, the distinct
+ * ARITH constant triples in a dictionary.  glp_witness_plan_create does every structural check of glp_witness_eval (indices < n_values, constants
+ * < p, shift / bit counts, op lengths, unknown kinds) and also refuses an operand that no earlier op wrote and a variable written twice:
+ * GLP_E_INVALID; GLP_E_UNSUPPORTED when n_values or n_inputs >= 2^32 - 1.  No GPU is needed for create / stats / run_host / destroy (as long
+ * as the plan was never evaluated on a device). */
+typedef struct glp_witness_plan glp_witness_plan;
+int glp_witness_plan_create(const uint64_t* prog, size_t prog_words, size_t n_inputs, size_t n_values, const uint64_t* eq_pairs, size_t n_eq,
+                            glp_witness_plan** plan);
+void glp_witness_plan_destroy(glp_witness_plan* plan);
+/* ops, levels, barrier-separated steps at the kernel's workgroup size (sum over levels of ceil(width / 256)), bytes resident per device.
+ * Any output pointer may be NULL. */
+int glp_witness_plan_stats(const glp_witness_plan* plan, uint64_t* n_ops, uint64_t* depth, uint64_t* steps, uint64_t* stream_bytes);
+/* the REORDERED schedule run serially on the host with the arithmetic of glp_witness_eval: same values, return code and *first_bad.  It exists
+ * so that a schedule can be checked without a GPU; glp_witness_eval_mt stays the host product path. */
+int glp_witness_plan_run_host(const glp_witness_plan* plan, const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag,
+                              const uint64_t* inputs, size_t n_inputs, uint64_t* values, size_t n_values, size_t* first_bad);
+/* B instances of the plan on the device, one workgroup per instance, level by level: d_inputs [B][n_inputs] -> d_values [B][value_stride]
+ * (value_stride >= n_values; words past n_values are left alone; a variable no op writes is set to 0), the layout glp_gather_u64 places wire cells from.  Stream-ordered on the ctx's
+ * stream, which is synchronised before the call returns.  GLP_OK when the batch ran; the verdict of instance b is h_status[b]: GLP_OK,
+ * GLP_E_REJECT (h_first_bad[b] = the lowest failing copy-constraint index, or (uint64_t)-1 when a row operand is out of range) or GLP_E_INVALID
+ * (an input word >= p) — an instance's verdict does not affect the others.  The plan's schedule is uploaded on first use per DEVICE and owned by
+ * the plan: shared by every ctx of that device, freed by glp_witness_plan_destroy (not by glp_destroy). */
+int glp_witness_eval_device(glp_ctx* ctx, const glp_witness_plan* plan, const uint64_t* d_inputs, uint64_t* d_values, size_t value_stride,
+                            uint32_t B, int32_t* h_status, uint64_t* h_first_bad);
 /* the Poseidon permutation on the host: n states of 12 canonical words, in place (same constants arguments as the host verifiers) */
 int glp_poseidon_permute_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, uint64_t* states, size_t n);
 int glp_plonk_proof_digest_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* h_proof,
