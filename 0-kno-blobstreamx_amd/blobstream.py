@@ -59,6 +59,100 @@ def encode_data_root_tuple(height: int, data_root: bytes) -> bytes:
     return height.to_bytes(32, "big") + data_root
 
 
+def canonical_vote_sign_bytes(chain_id, height, round, block_hash, part_total, part_hash, seconds, nanos, vote_type=2) -> bytes:
+    """[SPEC] recalled, unpinned: the sign-bytes of a Tendermint / CometBFT vote — protobuf ``CanonicalVote``, length-delimited (no upstream
+    source is in the mount: the layout below is restated from the public definition and pinned only by this repository's own tests).
+
+        varint(len(body)) ‖ body
+        body = 08 tt                      type (02 precommit, 01 prevote)
+               11 <height: 8 bytes LE>    sfixed64
+               19 <round: 8 bytes LE>     sfixed64, only when round != 0
+               22 LL  0a 20 <hash:32>  12 MM ( 08 varint(part_total)  12 20 <part_hash:32> )        CanonicalBlockID
+               2a NN  08 varint(seconds) [10 varint(nanos) when nanos != 0]                          google.protobuf.Timestamp
+               32 KK <chain_id>
+
+    Fields in number order; zero scalars and empty strings are omitted (proto3), embedded messages are always written.  Every validator signs
+    its OWN timestamp, so the votes of one commit differ in length by the nanos varint (absent, or 1 to 5 bytes)."""
+    chain = chain_id.encode() if isinstance(chain_id, str) else bytes(chain_id)
+    block_hash, part_hash = bytes(block_hash), bytes(part_hash)
+    if len(block_hash) != 32 or len(part_hash) != 32:
+        raise ValueError("block hash and part-set hash are 32 bytes")
+    if height <= 0 or height >= 1 << 63 or not 0 <= round < 1 << 63:
+        raise ValueError("height must be positive, round non-negative (sfixed64)")
+    if seconds < 0 or nanos < 0 or nanos >= 10**9:
+        raise ValueError("timestamp out of range: seconds >= 0, 0 <= nanos < 10^9")
+    if vote_type not in (1, 2) or part_total < 0:
+        raise ValueError("vote type is 1 (prevote) or 2 (precommit); part total is non-negative")
+    psh = (b"\x08" + encode_varint(part_total) if part_total else b"") + b"\x12\x20" + part_hash
+    block_id = b"\x0a\x20" + block_hash + b"\x12" + encode_varint(len(psh)) + psh
+    stamp = (b"\x08" + encode_varint(seconds) if seconds else b"") + (b"\x10" + encode_varint(nanos) if nanos else b"")
+    body = b"\x08" + bytes([vote_type]) + b"\x11" + struct.pack("<q", height)
+    if round:
+        body += b"\x19" + struct.pack("<q", round)
+    body += b"\x22" + encode_varint(len(block_id)) + block_id + b"\x2a" + encode_varint(len(stamp)) + stamp
+    if chain:
+        body += b"\x32" + encode_varint(len(chain)) + chain
+    return encode_varint(len(body)) + body
+
+
+class VoteFormat:
+    """What a signature circuit fixes about the canonical votes it accepts: whether the round field is present, and the window
+    [min_len, max_len] of TOTAL sign-bytes lengths (length prefix included).  Derived: ``prefix_len`` (bytes of the length prefix), ``base`` (offset
+    of the block id's tag 22) and ``hash_offset`` (offset of the 32 block-hash bytes).
+    STATED LIMITS (ValueError otherwise): the window must not straddle the 1-byte / 2-byte length prefix (max_len <= 128, or min_len >= 130 —
+    a total of 129 does not exist), and 48 <= min_len, max_len <= 175: exactly there SHA-512 of R ‖ A ‖ M is two blocks for every length of the
+    window, which is what lets one circuit hash all of them."""
+    __slots__ = ("round_present", "min_len", "max_len")
+
+    def __init__(self, round_present, min_len, max_len):
+        self.round_present, self.min_len, self.max_len = bool(round_present), int(min_len), int(max_len)
+        if self.min_len > self.max_len:
+            raise ValueError("empty length window")
+        if not (self.max_len <= 128 or self.min_len >= 130):
+            raise ValueError("the length window straddles the 1-byte / 2-byte length prefix: split it into two formats")
+        if self.min_len < 48 or self.max_len > 175:
+            raise ValueError("the length window leaves [48, 175]: SHA-512 of R || A || M is no longer two blocks for every length")
+        if self.hash_offset + 32 > self.min_len:
+            raise ValueError("the shortest vote of the window cannot hold the block hash")
+
+    @property
+    def prefix_len(self):
+        return 1 if self.max_len <= 128 else 2
+
+    @property
+    def base(self):
+        return self.prefix_len + 11 + (9 if self.round_present else 0)
+
+    @property
+    def hash_offset(self):
+        return self.base + 4
+
+    @classmethod
+    def for_commit(cls, chain_id, round, seconds_bytes=5, part_total_bytes=1):
+        """the format of the votes of ONE commit: chain id and round are the commit's, the seconds varint has seconds_bytes bytes (5 for any
+        date from 1978 to 3058), the part total part_total_bytes; the window spans the nanos field from omitted to 5 varint bytes"""
+        chain = chain_id.encode() if isinstance(chain_id, str) else bytes(chain_id)
+        psh = 1 + part_total_bytes + 34
+        block_id = 34 + 2 + psh
+        if block_id >= 128 or len(chain) >= 128 or not 1 <= seconds_bytes <= 9 or part_total_bytes < 1:
+            raise ValueError("field lengths outside the one-byte length forms this layout assumes")
+        body = 2 + 9 + (9 if round else 0) + 2 + block_id + 2 + (1 + seconds_bytes) + (2 + len(chain) if chain else 0)
+        lo, hi = body, body + 6
+        return cls(bool(round), lo + len(encode_varint(lo)), hi + len(encode_varint(hi)))
+
+    def __eq__(self, other):
+        return isinstance(other, VoteFormat) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def as_tuple(self):
+        return (self.round_present, self.min_len, self.max_len)
+
+    def __repr__(self):
+        return f"VoteFormat(round_present={self.round_present}, min_len={self.min_len}, max_len={self.max_len})"
+
+
 # ---- hashing witnesses (GPU) -------------------------------------------------------------------
 
 

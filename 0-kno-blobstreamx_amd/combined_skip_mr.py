@@ -12,8 +12,11 @@ Shape (build-defined statement, NOT upstream's circuit):
            starts at the trusted header's hash (as computed by the skip half), ends at the target header's hash, its first height is
            trusted block + 1 and the target block is trusted block + skip.
 Public inputs of the final proof (30 words, as gadgets.combined_skip_circuit's): trusted header hash (8), target header hash (8), signer digest
-(4), trusted block, target block, data commitment (8).  The Ed25519 half stays outside the circuit: the signer digest names who was flagged and
-``blobstream.verify_signers`` checks exactly those signatures natively — until the curve rows exist.
+(4), trusted block, target block, data commitment (8).  The Ed25519 half: without `signatures` it stays outside the circuit — the signer digest
+names who was flagged and ``blobstream.verify_signers`` checks exactly those signatures natively.  With a
+signature_mr.SignatureSetMapReduce the outer circuit also verifies the root of the signature MapReduce and equates its block hash and signer
+digest with the skip statement's; with a signature_mr.CanonicalVoteSetMapReduce the votes are canonical precommits of
+differing lengths and their height is equated with the target block as well (the round only has to be common to all slots).
 Which target validator is which trusted validator (`trusted_index`) and every length (set sizes, varint groups of powers / heights, field
 lengths) are CONSTANTS of the outer circuit: another shape is another circuit (and key).  Multi-GPU: rank r proves and folds the r-th contiguous
 part of the chain, ONE all-gather of node proofs, rank 0 folds the root and proves the outer circuit."""
@@ -65,6 +68,7 @@ class CombinedSkipMapReduce:
             return self.outer[k]
         t0 = time.perf_counter()
         skip = self.skip
+        canonical = sig_root is not None and getattr(self.sigs, "vote_format", None) is not None
 
         def combine(b, outs):
             g = Sha256Rows(b)
@@ -80,6 +84,9 @@ class CombinedSkipMapReduce:
                 ps = outs[1]["public"]                                # the signature set's root: block hash (8), signer digest (4)
                 for x, y in zip(hv + sd, ps[:12]):
                     b.assert_equal(x, y)                              # the votes name THE target header, the flags are the verified slots
+                if canonical:
+                    b.assert_equal(ps[12], blocks[1])                 # canonical votes: they are votes AT the target block's height
+                    b.assert_equal(ps[13], b.constant(0))             # (the high word of the sfixed64; the round, ps[14:16], is not exported)
             return ht + hv + sd + blocks + pub[16:24]
         chain_spec = dict(leaf_key=chain_key, n_public=HeaderChainMapReduce.N_PUBLIC, child_is_recursion=chain_is_node)
         proofs, specs = [chain_root], [chain_spec]
@@ -203,7 +210,10 @@ class CombinedSkipMapReduce:
         from .ed25519_circuit import keypair_and_sign
         _, _, chain, (vk, _), signed, _, _ = case
         target_hash = HeaderChainMapReduce.header_hash(chain[-1])
-        msgs = [self.sigs.vote_bytes(target_hash, i) for i in range(len(vk))]
+        if getattr(self.sigs, "vote_format", None) is not None:
+            msgs = [self.sigs.vote_bytes(target_hash, i, height=case[6] + self.skip) for i in range(len(vk))]      # canonical votes at the target height
+        else:
+            msgs = [self.sigs.vote_bytes(target_hash, i) for i in range(len(vk))]
         sigs = []
         for i, (key, sg) in enumerate(zip(vk, signed)):
             if not sg:

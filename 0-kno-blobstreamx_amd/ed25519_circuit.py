@@ -504,6 +504,10 @@ class Sha512Gadget:
         n = len(byte_bits)
         const_byte = lambda v: [self.one if (v >> i) & 1 else self.zero for i in range(8)]
         msg = list(byte_bits) + [const_byte(0x80)] + [const_byte(0)] * ((111 - n) % 128) + [const_byte(v) for v in (8 * n).to_bytes(16, "big")]
+        return self._hash_padded(msg)
+
+    def _hash_padded(self, msg):
+        """the compression chain over an already padded message (a whole number of 128-byte blocks of byte-bit lists)"""
         assert len(msg) % 128 == 0
         state = [self.const_word(v) for v in IV512]
         for off in range(0, len(msg), 128):
@@ -517,6 +521,47 @@ class Sha512Gadget:
             for j in range(8):                                                    # digest byte 8w + j = bits (7-j)*8 .. of word w
                 out.append(wd[0][(7 - j) * 8: (7 - j) * 8 + 8])
         return out
+
+    def hash_bytes_var(self, fixed_bytes, msg_bytes, min_len, max_len, onehot):
+        """SHA-512 of fixed_bytes ‖ M[:L] for a message whose length L, min_len <= L <= max_len, is a WITNESS: msg_bytes holds max_len bytes
+        (byte-bit lists as in hash_bytes), onehot = max_len - min_len + 1 variables of which exactly the one at L - min_len is 1.  Laid down here:
+        every onehot entry is boolean and their sum is 1; L = min_len + sum j * onehot[j]; for a position p of the window the hashed byte is
+        (sum_{j > p - min_len} onehot[j]) * M[p] + onehot[p - min_len] * 0x80 — the message below L, the padding's 0x80 at L, zero above — so
+        the bytes of msg_bytes at or beyond L do not reach the digest; the length field 8 * (len(fixed) + L) comes from a boolean decomposition
+        packed back to that value.  Every length of the window must pad to the same number of blocks (ValueError otherwise).
+        Returns (the 64 digest bytes as in hash_bytes, the variable L)."""
+        b = self.b
+        nf, W = len(fixed_bytes), max_len - min_len + 1
+        if len(msg_bytes) != max_len or len(onehot) != W or W < 1:
+            raise ValueError("max_len message bytes and one selector per length of the window")
+        n_blocks = (nf + max_len + 17 + 127) // 128
+        if (nf + min_len + 17 + 127) // 128 != n_blocks:
+            raise ValueError("the lengths of the window do not all pad to the same number of SHA-512 blocks")
+        total, length = None, None
+        for j, s in enumerate(onehot):
+            b.assert_bool(s)
+            total = s if total is None else b.arith(1, 1, 0, s, self.one, total)
+            length = b.arith(0, 0, min_len, s, s, s) if length is None else b.arith(j, 1, 0, s, self.one, length)
+        b.assert_equal(total, self.one)                                          # exactly one length
+        above = [None] * W                                                       # above[i] = sum_{j > i} onehot[j]: 1 iff L > min_len + i
+        for i in range(W - 2, -1, -1):
+            above[i] = onehot[i + 1] if above[i + 1] is None else b.arith(1, 1, 0, onehot[i + 1], self.one, above[i + 1])
+        msg = list(fixed_bytes) + list(msg_bytes[:min_len])
+        for i in range(W - 1):
+            m = msg_bytes[min_len + i]
+            msg.append([b.arith(1, 0, 0, above[i], bit, above[i]) for bit in m[:7]] + [b.arith(1, 1, 0, above[i], m[7], onehot[i])])
+        msg.append([self.zero] * 7 + [onehot[W - 1]])                            # position max_len: the 0x80 of the longest message
+        msg += [[self.zero] * 8] * (128 * n_blocks - 16 - len(msg))
+        n_bits = (8 * (nf + max_len)).bit_length()
+        assert n_bits <= 16
+        field = b.arith(8, 0, 8 * nf, length, self.one, length)                   # the message length in bits
+        fbits = [b.bit(field, i) for i in range(n_bits)]
+        for bit in fbits:
+            b.assert_bool(bit)
+        b.assert_equal(self.pack(fbits), field)
+        fbits += [self.zero] * (16 - n_bits)
+        msg += [[self.zero] * 8] * 14 + [fbits[8:16], fbits[0:8]]
+        return self._hash_padded(msg), length
 
 
 # ---- the statement ---------------------------------------------------------------------------------------------------------------------------
@@ -534,6 +579,47 @@ def _limbs_from_byte_bits(g, byte_bits, n_limbs):
     """little-endian integer of the bytes as 24-bit limbs (three bytes each; a last limb may be shorter): packed from the bits"""
     flat = [bit for byte in byte_bits for bit in byte]
     return [g.pack(flat[LB * i: LB * i + LB]) for i in range(n_limbs) if flat[LB * i: LB * i + LB]]
+
+
+def _vote_format_constraints(b, f, it, own_msg, flag_var, fmt):
+    """verify_statement's canonical-vote half: reads the own length L and its one-hot selectors from the input iterator, constrains the slot's
+    own bytes to the format (see verify_statement), and returns ({"length", "height_words", "round_words"}, the one-hot of the HASHED length:
+    the own one when the flag is 1, min_len's when it is 0)"""
+    lo, hi, pl, base = fmt.min_len, fmt.max_len, fmt.prefix_len, fmt.base
+    W = hi - lo + 1
+    L = b.var(next(it))
+    onehot = [b.var(next(it)) for _ in range(W)]
+    total, length = None, None
+    for j, s in enumerate(onehot):
+        b.assert_bool(s)
+        total = s if total is None else b.arith(1, 1, 0, s, f.one, total)
+        length = b.arith(0, 0, lo, s, s, s) if length is None else b.arith(j, 1, 0, s, f.one, length)
+    b.assert_equal(total, f.one)
+    b.assert_equal(length, L)                                                    # min_len <= L <= max_len, and the selectors spell it
+    byte = lambda p: own_msg[p][0]
+    is_const = lambda p, v: b.assert_equal(byte(p), b.constant(v))
+    b.assert_equal(b.arith(1, 0, pl, byte(0), f.one, byte(0)), L)                # the length prefix: body length = L - prefix_len ...
+    if pl == 2:
+        is_const(1, 1)                                                           # ... as the two-byte varint (0x80 | low 7 bits, 1) of 128 .. 255
+    for p, v in ((pl, 0x08), (pl + 1, 0x02), (pl + 2, 0x11), (base, 0x22), (base + 2, 0x0A), (base + 3, 0x20)):
+        is_const(p, v)
+    if fmt.round_present:
+        is_const(pl + 11, 0x19)
+    b.assert_equal(own_msg[base + 1][1][7], f.zero)                              # the block id's length is ONE varint byte
+    def words_le(p):
+        bs = [byte(p + k) for k in range(8)]
+        word = lambda q: b.arith(1 << 24, 1, 0, q[3], f.one, b.arith(1 << 16, 1, 0, q[2], f.one, b.arith(1 << 8, 1, 0, q[1], f.one, q[0])))
+        return [word(bs[:4]), word(bs[4:])]
+    # flag ? own length : min_len.  Selector 0 takes what the others leave, so exactly one is set either way
+    if W == 1:
+        sel = [f.one]
+    else:
+        sel = [b.arith(1, 0, 0, flag_var, s, flag_var) for s in onehot[1:]]
+        rest = sel[0]
+        for s in sel[1:]:
+            rest = b.arith(1, 1, 0, s, f.one, rest)
+        sel = [b.arith(P - 1, 0, 1, rest, f.one, rest)] + sel
+    return {"length": L, "height_words": words_le(pl + 3), "round_words": words_le(pl + 12) if fmt.round_present else [f.zero, f.zero]}, sel
 
 
 HALF_NIBBLES = 36                     # windows of the half-size scalars: 144 bits (a reduced basis vector longer than that has probability ~2^-36)
@@ -582,16 +668,28 @@ def dummy_signature(msg_len):
     return _DUMMY[msg_len]
 
 
-def witness_inputs(pub32, sig64, msg, flag=None, record=None, split_scalars=True):
+def witness_inputs(pub32, sig64, msg, flag=None, record=None, split_scalars=True, vote_format=None):
     """the input vector of a program recorded from verify_statement for a message of this length, in the order the statement creates its free
     variables: [with a flag: the flag, the validator's key bytes, the message bytes, then for the VERIFIED triple — the validator's own when the
     flag is 1, dummy_signature's when it is 0 —] A bytes, R bytes, S bytes, message bytes [without a flag only], then the limbs of x_A, x_R, of
     the quotient t and of k = SHA-512(R || A || M) mod L.  ValueError when A or R does not decode (no witness exists).
     record: the 37-word record of the GPU witness kernel for the VERIFIED triple (glp_ed25519_witness: verdict, k, decoded A and R ...): x_A, x_R
-    and k are then taken from the device's computation instead of being recomputed with Python integers (the circuit checks them either way)."""
+    and k are then taken from the device's computation instead of being recomputed with Python integers (the circuit checks them either way).
+    vote_format (a blobstream.VoteFormat; needs a flag): msg has its TRUE length, anywhere in the format's window.  The head is then the flag, the
+    key bytes, the message zero-padded to max_len bytes, the length L, and the one-hot selectors of L - min_len; the dummy triple of an unflagged
+    slot is dummy_signature(min_len)'s.  ValueError for a length outside the window."""
     pub32, msg = bytes(pub32), bytes(msg)
     head = []
-    if flag is not None:
+    if vote_format is not None:
+        if flag is None:
+            raise ValueError("a vote format needs the flagged form of the statement")
+        lo, hi = vote_format.min_len, vote_format.max_len
+        if not lo <= len(msg) <= hi:
+            raise ValueError(f"a vote of {len(msg)} bytes is outside this circuit's window [{lo}, {hi}]")
+        head = [1 if flag else 0] + list(pub32) + list(msg.ljust(hi, b"\0")) + [len(msg)] + [1 if j == len(msg) - lo else 0 for j in range(hi - lo + 1)]
+        if not flag:
+            pub32, sig64, msg = dummy_signature(lo)
+    elif flag is not None:
         head = [1 if flag else 0] + list(pub32) + list(msg)
         if not flag:
             pub32, sig64, msg = dummy_signature(len(msg))
@@ -623,15 +721,21 @@ def witness_inputs(pub32, sig64, msg, flag=None, record=None, split_scalars=True
     return out + limbs_of(u, 6) + limbs_of(v, 6) + [1 if neg else 0] + limbs_of(q1, 7) + limbs_of(w) + limbs_of(q2, 7)
 
 
-def verify_statement(b, pub32, sig64, msg, flag=None, split_scalars=True):
+def verify_statement(b, pub32, sig64, msg, flag=None, split_scalars=True, vote_format=None):
     """Lay down, on builder b (144 wires: the range checks use ADD rows), the verification of ONE Ed25519 signature (RFC 8032 §5.1.7, equation
     [S]B = R + [k]A).  Free inputs in witness_inputs' order.  flag (None, or the slot's `signed` value): with a flag the statement is
     "flag = 1  =>  sig64 is the key's signature of msg" — the key and message that enter the verification are SELECTED by the flag between the
     slot's own and dummy_signature's (a slot that did not sign verifies the fixed dummy triple), so one circuit serves signers and non-signers.
     Returns {"key_words": 8 big-endian 32-bit word variables of the slot's public key, "msg_bytes": the message byte variables,
-    "flag": the flag variable or None, "stats": {...}}.  ValueError when the signature does not verify (some constraint fails on its witness)."""
+    "flag": the flag variable or None, "stats": {...}}.  ValueError when the signature does not verify (some constraint fails on its witness).
+    vote_format (a blobstream.VoteFormat; needs a flag): msg is a CANONICAL VOTE of any length L of the format's window, one circuit for all of
+    them (free inputs: witness_inputs' order).  The slot's own max_len bytes are constrained UNCONDITIONALLY (also when the flag is 0): the length
+    prefix spells L - prefix_len, 08 02 (a precommit) and the tag 11 of the height follow it, 19 opens the round when the format has one, the
+    block id starts at `base` with 22, a one-byte length, 0a 20 — which pins the block hash to hash_offset —, and min_len <= L <= max_len (the
+    one-hot).  What is hashed is flag ? (key, vote, L) : (dummy_signature(min_len), min_len), through Sha512Gadget.hash_bytes_var.  The dict then
+    also has "height_words" and "round_words": (lo, hi) 32-bit words of the little-endian sfixed64 fields (round: the constant 0 when absent)."""
     pub32, msg = bytes(pub32), bytes(msg)
-    vals = witness_inputs(pub32, sig64, msg, flag, split_scalars=split_scalars)
+    vals = witness_inputs(pub32, sig64, msg, flag, split_scalars=split_scalars, vote_format=vote_format)
     it = iter(vals)
     f = NNF(b)
     g = Sha512Gadget(b)
@@ -651,8 +755,10 @@ def verify_statement(b, pub32, sig64, msg, flag=None, split_scalars=True):
         flag_var = b.var(next(it))
         b.assert_bool(flag_var)
         own_key = [_byte_input(b, g, next(it)) for _ in range(32)]
-        own_msg = [_byte_input(b, g, next(it)) for _ in range(len(msg))]
-        d_pub, _, d_msg = dummy_signature(len(msg))
+        own_msg = [_byte_input(b, g, next(it)) for _ in range(len(msg) if vote_format is None else vote_format.max_len)]
+        if vote_format is not None:
+            fmt_out, sel_onehot = _vote_format_constraints(b, f, it, own_msg, flag_var, vote_format)
+        d_pub, _, d_msg = dummy_signature(len(msg) if vote_format is None else vote_format.min_len)
         # flag ? own : dummy  =  dummy + flag * (own - dummy), byte by byte; the selected byte is decomposed again (it feeds the hash)
         pick = lambda own, dv: decomposed(b.arith(1, 0, dv, flag_var, b.arith(1, 0, P - dv, own, f.one, own), flag_var))
         A_bytes = [pick(v, dv) for (v, _), dv in zip(own_key, d_pub)]
@@ -661,7 +767,7 @@ def verify_statement(b, pub32, sig64, msg, flag=None, split_scalars=True):
     if flag is None:
         M_bytes = [_byte_input(b, g, next(it)) for _ in range(len(msg))]
         own_msg = M_bytes
-    else:
+    elif vote_format is None:
         M_bytes = [pick(v, dv) for (v, _), dv in zip(own_msg, d_msg)]
     x_a, x_r = f.witness(sum(next(it) << (LB * i) for i in range(NL))), f.witness(sum(next(it) << (LB * i) for i in range(NL)))
     t_q = f.witness(sum(next(it) << (LB * i) for i in range(NL)))
@@ -680,7 +786,14 @@ def verify_statement(b, pub32, sig64, msg, flag=None, split_scalars=True):
     f.assert_le_const(s_limbs, ELL - 1)
     s_nibbles = [s_bits[4 * w: 4 * w + 4] for w in range(64)]
     # k = SHA-512(R || A || M) mod L:  h = t * L + k over the integers, k < L
-    digest = g.hash_bytes([byte for _, byte in R_bytes] + [byte for _, byte in A_bytes] + [byte for _, byte in M_bytes])
+    if vote_format is None:
+        digest = g.hash_bytes([byte for _, byte in R_bytes] + [byte for _, byte in A_bytes] + [byte for _, byte in M_bytes])
+    else:
+        # the dummy message is all zeros: flag ? own : dummy is flag * own, bit by bit (products of booleans: no second decomposition)
+        assert not any(d_msg)
+        m_sel = [[b.arith(1, 0, 0, flag_var, bit, flag_var) for bit in bits] for _, bits in own_msg]
+        digest, _ = g.hash_bytes_var([byte for _, byte in R_bytes] + [byte for _, byte in A_bytes], m_sel, vote_format.min_len, vote_format.max_len,
+                                     sel_onehot)
     h_limbs = _limbs_from_byte_bits(g, digest, 22)
     f.assert_le_const(k_s.limbs, ELL - 1)
     ell = limbs_of(ELL)
@@ -786,7 +899,10 @@ def verify_statement(b, pub32, sig64, msg, flag=None, split_scalars=True):
         bs = [own_key[4 * wd + j][0] for j in range(4)]
         hi = b.arith(1 << 24, 1, 0, bs[0], f.one, b.arith(1 << 16, 0, 0, bs[1], f.one, bs[1]))
         key_words.append(b.arith(1 << 8, 1, 0, bs[2], f.one, b.arith(1, 1, 0, hi, f.one, bs[3])))
-    return {"key_words": key_words, "msg_bytes": [v for v, _ in own_msg], "flag": flag_var, "stats": {"field_products": f.n_mul}}
+    out = {"key_words": key_words, "msg_bytes": [v for v, _ in own_msg], "flag": flag_var, "stats": {"field_products": f.n_mul}}
+    if vote_format is not None:
+        out.update(fmt_out)
+    return out
 
 
 def ed25519_circuit(prover, pub32, sig64, msg):

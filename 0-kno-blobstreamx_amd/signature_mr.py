@@ -13,7 +13,11 @@ The root therefore says: "every slot flagged in the signer digest D carries a va
 hash H".  combined_skip_mr.py verifies that root inside the CombinedSkip outer circuit and equates (H, D) with the target header hash and the
 signer digest its voting-power rules were computed from — the signatures are then part of the proof, not a native side check.
 Slots are padded to a power of two with all-zero keys and flag 0 (the padding gadgets._signer_digest uses).  Vote bytes are opaque except for
-the block hash (build-defined stand-in for the canonical vote encoding: fixed length, hash at a fixed offset).  Everything here is build-defined."""
+the block hash (build-defined stand-in for the canonical vote encoding: fixed length, hash at a fixed offset).  Everything here is build-defined.
+
+``CanonicalVoteSetMapReduce`` is the same MapReduce over CANONICAL votes (blobstream.canonical_vote_sign_bytes) of differing lengths: one leaf
+circuit for every length of a blobstream.VoteFormat window, the vote's type, tags and length prefix constrained, and height and round carried
+to the root next to the block hash (leaf: 21 public inputs, nodes: 16)."""
 import importlib
 import struct
 import time
@@ -29,8 +33,20 @@ from .recursion import CircuitBuilder
 LEAF_PUBLIC = 17
 
 
+def _hash_words(b, hb):
+    """big-endian 32-bit words of 32 byte variables"""
+    one = b.constant(1)
+    words = []
+    for k in range(0, 32, 4):
+        hi = b.arith(1 << 24, 1, 0, hb[k], one, b.arith(1 << 16, 0, 0, hb[k + 1], one, hb[k + 1]))
+        words.append(b.arith(1 << 8, 1, 0, hb[k + 2], one, b.arith(1, 1, 0, hi, one, hb[k + 3])))
+    return words
+
+
 class SignatureSetMapReduce(DataCommitmentMapReduce):
     N_PUBLIC = 12                                   # nodes: block hash (8), signer-digest subtree (4)
+    N_TAIL = 0                                      # further words every leaf and node carries after those, required equal across children
+    vote_format = None                              # a blobstream.VoteFormat in CanonicalVoteSetMapReduce
 
     def __init__(self, prover, poseidon_consts, msg_len=112, hash_offset=16, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
                  device_witness_chunk=32):
@@ -41,7 +57,7 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         self.msg_len, self.hash_offset = int(msg_len), int(hash_offset)
 
     def _child_n_public(self, level):
-        return LEAF_PUBLIC if level == 1 else self.N_PUBLIC
+        return LEAF_PUBLIC + self.N_TAIL if level == 1 else self.N_PUBLIC
 
     def _child_has_poseidon_rows(self, level):
         return level > 1                             # a signature leaf is arithmetic gates and ADD rows only
@@ -53,19 +69,19 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         return level == 1                            # ... and the nodes above have Poseidon rows and arithmetic only
 
     def _combine_for(self, span):
-        leaf_children = span == 1
+        leaf_children, T = span == 1, self.N_TAIL
 
         def combine(b, outs):
             if leaf_children:
-                hashes = [o["public"][9:17] for o in outs]
+                hashes = [o["public"][9:17] + o["public"][17:17 + T] for o in outs]
                 leaves = [signer_leaf(b, o["public"][:8], o["public"][8]) for o in outs]
             else:
-                hashes = [o["public"][:8] for o in outs]
+                hashes = [o["public"][:8] + o["public"][12:12 + T] for o in outs]
                 leaves = [o["public"][8:12] for o in outs]
             for other in hashes[1:]:
                 for x, y in zip(hashes[0], other):
-                    b.assert_equal(x, y)                                      # every slot's vote names the SAME block
-            return hashes[0] + signer_tree(b, leaves)
+                    b.assert_equal(x, y)                                      # every slot's vote names the SAME block (and height, round)
+            return hashes[0][:8] + signer_tree(b, leaves) + hashes[0][8:]
         return combine
 
     # ---- Map ------------------------------------------------------------------------------------------------------------------------------
@@ -81,12 +97,7 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         pub, sig = keypair_and_sign(bytes(32), msg)
         b = CircuitBuilder(self.prover, n_wires=SHA_GATE_WIRES, n_routed=SHA_GATE_WIRES)
         st = verify_statement(b, pub, sig, msg, flag=True)
-        one = b.constant(1)
-        hb = st["msg_bytes"][self.hash_offset:self.hash_offset + 32]
-        words = []
-        for k in range(0, 32, 4):                                              # big-endian words of the block hash bytes
-            hi = b.arith(1 << 24, 1, 0, hb[k], one, b.arith(1 << 16, 0, 0, hb[k + 1], one, hb[k + 1]))
-            words.append(b.arith(1 << 8, 1, 0, hb[k + 2], one, b.arith(1, 1, 0, hi, one, hb[k + 3])))
+        words = _hash_words(b, st["msg_bytes"][self.hash_offset:self.hash_offset + 32])      # big-endian words of the block hash bytes
         for v in st["key_words"] + [st["flag"]] + words:
             b.public_input(v)
         self.leaf_program = b.program()
@@ -95,14 +106,20 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         self.leaf_stats = dict(self.leaf_program.stats, field_products=st["stats"]["field_products"])
         self.record_seconds["leaf"] = round(time.perf_counter() - t0, 3)
 
+    def _check_slot(self, pubkey, msg):
+        if len(bytes(msg)) != self.msg_len or len(bytes(pubkey)) != 32:
+            raise ValueError("vote bytes / key of another length than this circuit was recorded for")
+
+    def _dummy_len(self):
+        return self.msg_len
+
     def prove_leaf(self, pubkey, signature, msg, flag, which=0):
         """(proof, public) for one slot; a slot with flag 0 needs no signature (None)"""
         if self.leaf_program is None:
             self._record_leaf()
-        if len(bytes(msg)) != self.msg_len or len(bytes(pubkey)) != 32:
-            raise ValueError("vote bytes / key of another length than this circuit was recorded for")
+        self._check_slot(pubkey, msg)
         prover, circuit = (self.prover, self.leaf_circuit) if which == 0 else (self.map_provers[which - 1], self.map_circuits[which - 1])
-        inputs = witness_inputs(pubkey, signature if flag else bytes(64), msg, bool(flag))
+        inputs = witness_inputs(pubkey, signature if flag else bytes(64), msg, bool(flag), vote_format=self.vote_format)
         vals = self.leaf_program.evaluate(self.consts, inputs, threads=1)
         dw, public = self.leaf_program.device_witness(prover, vals, reuse=True)
         return circuit.prove_(dw, self.nq, self.pw, public=public), public
@@ -121,9 +138,8 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         kernel north_star names for this job); a flagged slot the kernel rejects is refused here, before any witness program runs."""
         from .ed25519_circuit import dummy_signature
         for i in range(lo, hi):
-            if len(bytes(slots[2][i])) != self.msg_len or len(bytes(slots[0][i])) != 32:
-                raise ValueError("vote bytes / key of another length than this circuit was recorded for")
-        d_pub, d_sig, d_msg = dummy_signature(self.msg_len)
+            self._check_slot(slots[0][i], slots[2][i])
+        d_pub, d_sig, d_msg = dummy_signature(self._dummy_len())
         triples = [(slots[0][i], slots[1][i], slots[2][i]) if slots[3][i] else (d_pub, d_sig, d_msg) for i in range(lo, hi)]
         if any(t[1] is None or len(bytes(t[1])) != 64 for t in triples):
             raise ValueError("a flagged slot has no 64-byte signature")
@@ -131,8 +147,8 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         bad = [lo + j for j in range(len(triples)) if not int(recs[j][0])]
         if bad:
             raise ValueError(f"the signatures of slots {bad[:8]} do not verify (GPU witness kernel)")
-        return self._map_inputs([witness_inputs(slots[0][i], slots[1][i] if slots[3][i] else bytes(64), slots[2][i], slots[3][i], record=recs[i - lo])
-                                 for i in range(lo, hi)])
+        return self._map_inputs([witness_inputs(slots[0][i], slots[1][i] if slots[3][i] else bytes(64), slots[2][i], slots[3][i], record=recs[i - lo],
+                                                vote_format=self.vote_format) for i in range(lo, hi)])
 
     def prove_set(self, pubkeys, signatures, msgs, flags):
         """one proof for a validator set's signatures: public = block hash (8 words), signer digest (4 words).  signatures[i] may be None where
@@ -169,16 +185,16 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         k = ("padded_root", len(nodes), total_groups, bytes(np.ascontiguousarray(child_key, dtype=np.uint64)))
         t0 = time.perf_counter()
         if k not in self.nodes:
-            F = self.fan_in
+            F, T = self.fan_in, self.N_TAIL
 
             def combine(b, outs):
-                hashes = [o["public"][:8] for o in outs]
+                hashes = [o["public"][:8] + o["public"][12:12 + T] for o in outs]
                 for other in hashes[1:]:
                     for x, y in zip(hashes[0], other):
                         b.assert_equal(x, y)
                 zero = b.constant(0)
                 pad_group = signer_tree(b, [signer_leaf(b, [zero] * 8, zero)] * F)
-                return hashes[0] + signer_tree(b, [o["public"][8:12] for o in outs] + [pad_group] * (total_groups - len(outs)))
+                return hashes[0][:8] + signer_tree(b, [o["public"][8:12] for o in outs] + [pad_group] * (total_groups - len(outs))) + hashes[0][8:]
             spec = dict(leaf_key=child_key, n_public=self.N_PUBLIC, child_is_recursion=True, child_sha=False)
             self.nodes[k] = vc.RecursionProgram(self.prover, nodes, child_key, self.nq, self.pw, SHA_GATE_WIRES, self.consts, n_routed=80,
                                                 n_public=self.N_PUBLIC, cap_height=1, child_is_recursion=True, child_sha=False, combine=combine,
@@ -234,4 +250,80 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
 
     def verify_set(self, root_proof, key, block_hash, signer_digest):
         public = list(struct.unpack(">8I", bytes(block_hash))) + [int(v) for v in signer_digest]
+        return bool(self.prover.plonk_verify(root_proof, key, self.nq, self.pw, public=public))
+
+
+class CanonicalVoteSetMapReduce(SignatureSetMapReduce):
+    """SignatureSetMapReduce over canonical Tendermint votes (blobstream.canonical_vote_sign_bytes) whose lengths differ inside the window of a
+    blobstream.VoteFormat: ONE leaf circuit serves every length (ed25519_circuit.verify_statement with vote_format), and besides the block hash it
+    pins the vote's type (precommit), tags and length prefix and exports height and round.
+    Leaf public inputs (21): key words (8), flag, block-hash words (8), height (lo, hi), round (lo, hi).
+    Node public inputs (16): block hash (8), signer digest (4), height (2), round (2) — the first 12 as in SignatureSetMapReduce; hash, height
+    and round are required equal across the children of every node.  Timestamp and chain id stay opaque bytes.
+    chain_id / round / part_total / part_hash / seconds: what vote_bytes (synthetic votes: expected_key, tests, bench) fills in around the block
+    hash; they must produce votes of this format."""
+    N_PUBLIC = 16
+    N_TAIL = 4
+    _NANOS = (0, 5, 300, 70_000, 3_000_000, 999_999_999)                      # varints of 0 (field omitted), 1, 2, 3, 4 and 5 bytes
+
+    def __init__(self, prover, poseidon_consts, vote_format, chain_id="celestia", round=0, part_total=1, part_hash=bytes(32), seconds=1_700_000_000,
+                 fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False, device_witness_chunk=32):
+        DataCommitmentMapReduce.__init__(self, prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
+                                         map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk)
+        if bool(round) != vote_format.round_present:
+            raise ValueError("the vote format and the round disagree about the round field")
+        self.vote_format = vote_format
+        self.msg_len, self.hash_offset = vote_format.max_len, vote_format.hash_offset
+        self.chain_id, self.round, self.part_total, self.part_hash, self.seconds = chain_id, int(round), int(part_total), bytes(part_hash), int(seconds)
+
+    def _check_slot(self, pubkey, msg):
+        if not self.vote_format.min_len <= len(bytes(msg)) <= self.vote_format.max_len or len(bytes(pubkey)) != 32:
+            raise ValueError(f"a vote outside this circuit's length window [{self.vote_format.min_len}, {self.vote_format.max_len}], or a key that is not 32 bytes")
+
+    def _dummy_len(self):
+        return self.vote_format.min_len
+
+    def vote_bytes(self, block_hash, slot=0, height=1, vote_type=2):
+        """validator `slot`'s canonical vote for this block at this height: its own timestamp, whose nanos varint length goes through every case
+        (omitted, 1 .. 5 bytes) with the slot number — the votes of one set differ in length"""
+        bs = importlib.import_module(__package__ + ".blobstream")
+        msg = bs.canonical_vote_sign_bytes(self.chain_id, height, self.round, block_hash, self.part_total, self.part_hash, self.seconds + slot,
+                                           self._NANOS[slot % len(self._NANOS)], vote_type=vote_type)
+        if not self.vote_format.min_len <= len(msg) <= self.vote_format.max_len:
+            raise ValueError("this object's chain id / timestamp / part total give votes outside its format's window")
+        return msg
+
+    def _record_leaf(self):
+        t0 = time.perf_counter()
+        msg = self.vote_bytes(bytes(32))
+        pub, sig = keypair_and_sign(bytes(32), msg)
+        b = CircuitBuilder(self.prover, n_wires=SHA_GATE_WIRES, n_routed=SHA_GATE_WIRES)
+        st = verify_statement(b, pub, sig, msg, flag=True, vote_format=self.vote_format)
+        words = _hash_words(b, st["msg_bytes"][self.hash_offset:self.hash_offset + 32])
+        for v in st["key_words"] + [st["flag"]] + words + st["height_words"] + st["round_words"]:
+            b.public_input(v)
+        self.leaf_program = b.program()
+        self.leaf_circuit = self.leaf_program.setup(self.prover)
+        self.map_circuits = [self.leaf_program.setup(p) for p in self.map_provers]
+        self.leaf_stats = dict(self.leaf_program.stats, field_products=st["stats"]["field_products"])
+        self.record_seconds["leaf"] = round(time.perf_counter() - t0, 3)
+
+    @staticmethod
+    def _with_height_and_round(out):
+        public = out["public"]
+        if public is not None:
+            out.update(height=int(public[12]) | int(public[13]) << 32, round=int(public[14]) | int(public[15]) << 32)
+        return out
+
+    def prove_set(self, pubkeys, signatures, msgs, flags):
+        """SignatureSetMapReduce.prove_set; public = block hash (8 words), signer digest (4), height (lo, hi), round (lo, hi), also given as
+        "height" and "round".  ValueError too when a vote is no precommit of this format or the votes differ in height or round."""
+        return self._with_height_and_round(super().prove_set(pubkeys, signatures, msgs, flags))
+
+    def prove_set_distributed(self, pubkeys, signatures, msgs, flags, device=None, comm=None):
+        return self._with_height_and_round(super().prove_set_distributed(pubkeys, signatures, msgs, flags, device=device, comm=comm))
+
+    def verify_set(self, root_proof, key, block_hash, signer_digest, height, round):
+        public = list(struct.unpack(">8I", bytes(block_hash))) + [int(v) for v in signer_digest] + \
+            [int(height) & 0xFFFFFFFF, int(height) >> 32, int(round) & 0xFFFFFFFF, int(round) >> 32]
         return bool(self.prover.plonk_verify(root_proof, key, self.nq, self.pw, public=public))
