@@ -207,6 +207,13 @@ def load_library():
         "glp_witness_plan_stats": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
         "glp_witness_plan_run_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
         "glp_witness_eval_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp]),
+        "glp_witness_plan_create_ex": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                                      ctypes.POINTER(_vp)]),
+        "glp_witness_plan_parts": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32), _vp, _vp, _vp]),
+        "glp_witness_check_words": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32,
+                                                   _vp, _vp]),
+        "glp_witness_check_words_host": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32,
+                                                        _vp, _vp]),
         "glp_gather_u64": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t]),
         "glp_field_params": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
         "glp_comm_unique_id": (ctypes.c_int, [_vp]),

@@ -35,13 +35,17 @@ N_PUBLIC = 30
 
 class CombinedSkipMapReduce:
     def __init__(self, prover, poseidon_consts, skip, batch=8, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), height_varint_bytes=4,
-                 field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), max_skip=1 << 20, chain=None, signatures=None):
+                 field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), max_skip=1 << 20, chain=None, signatures=None,
+                 device_witness=False):
         """chain: a HeaderChainMapReduce of the same batch / fan-in / parameters to SHARE (its leaf and node recordings serve every skip length;
         it is then not freed by free()).
         signatures: a signature_mr.SignatureSetMapReduce (same query / PoW parameters): prove_skip(..., votes=(signatures, vote bytes)) then
         ALSO proves the target validators' Ed25519 signatures (one leaf per slot, folded to a root) and the outer circuit verifies that root and
         equates its block hash with the target header hash and its signer digest with the one the power rules were computed from — the
-        statement is then complete, signatures included.  Not freed by free()."""
+        statement is then complete, signatures included.  Not freed by free().
+        device_witness: the OUTER circuit's witness is evaluated and word-checked on the device (RecursionProgram.prove(device_witness=True):
+        its children are proofs of different circuits, so its segments have different lengths); the chain and signature objects carry their own
+        keyword."""
         if skip % batch or skip < batch:
             raise ValueError("skip must be a whole number of batches")
         self.prover, self.consts = prover, tuple(np.ascontiguousarray(a, dtype=np.uint64) for a in poseidon_consts)
@@ -55,6 +59,7 @@ class CombinedSkipMapReduce:
         self.outer = {}                  # (chain root key, trusted_index, ..., signature root key) -> RecursionProgram
         self.record_seconds = {}
         self.sigs = signatures
+        self.device_witness = bool(device_witness)
         if signatures is not None and (signatures.nq, signatures.pw) != (num_queries, pow_bits):
             raise ValueError("the signature MapReduce has other parameters")
 
@@ -114,7 +119,8 @@ class CombinedSkipMapReduce:
         t0 = time.perf_counter()
         words = np.array(skip_statement_inputs(tf, trusted, vf, target, signed, heights=(h0, h0 + self.skip)), dtype=np.uint64)
         # word lists in the order the outer circuit tagged them: the verified proofs first, the skip statement's witness last
-        proof, public = rp.prove([root_chain] + ([sig_root] if sig_root is not None else []) + [words], self.nq, self.pw)
+        proof, public = rp.prove([root_chain] + ([sig_root] if sig_root is not None else []) + [words], self.nq, self.pw,
+                                  device_witness=self.device_witness)
         t1 = time.perf_counter()
         be = lambda ws: b"".join(struct.pack(">I", v) for v in ws)
         return {"root_proof": proof, "public": public, "key": rp.key(), "outer_seconds": round(t1 - t0, 4), "chain_seconds": round(t_chain, 4),

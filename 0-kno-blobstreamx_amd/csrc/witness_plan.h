@@ -15,7 +15,15 @@
 // A variable that NO op writes (a recorded circuit may hold some; they can sit in wire cells) is 0: the host evaluator leaves such a word as the
 // caller passed it and WitnessProgram.evaluate passes zeros, so the plan lists those variables and its executors write the zeros themselves.
 // A RUN is a maximal range of one level's ops of one kind: {kind, count, word offset}; level l owns runs [level_run[l], level_run[l + 1]).
-// This header is host + device C++ with no HIP runtime dependency: the CPU emulation (tests/emu_witness) compiles it unchanged.
+// PARTS.  A recursion node is one instance whose ops are fan-in mutually independent verifier segments (the seg_bounds of glp_witness_eval_mt:
+// n_seg + 1 ascending word offsets on op boundaries).  glp_wit_compile_ex cuts such a program into n_seg + 2 parts — the prefix
+// [0, seg_bounds[0]), one part per segment, the tail — and gives each part its OWN level schedule: the level of an op counts only producers
+// inside its part (what an earlier part wrote is simply there).  The parts' levels are laid one after the other in the one level_run / runs /
+// stream, part s owning levels [part_level[s], part_level[s + 1]): walking all levels in order runs the parts in order (glp_wit_run_host, and
+// the single-workgroup kernel, stay correct on a segmented plan), while glp_witness_eval_part_kernel gives every segment a workgroup of its own.
+// The independence claim (an op of segment s reads only what the prefix or segment s wrote) is checked HERE: the kernel has no checks.
+// This header is host + device C++ with no HIP runtime dependency: the CPU emulation (tests/emu_witness, tests/emu_witness_seg) compiles it
+// unchanged.
 #pragma once
 #include <stdint.h>
 #include <map>
@@ -144,10 +152,14 @@ GL_HD int glp_wit_exec(u32 kind, const u32* __restrict__ r, const u64* __restric
     }
 }
 
+struct glp_wit_part { u64 n_ops, steps; u32 depth; };       // one part's share of the schedule (steps at GLP_WIT_WG lanes)
+
 struct glp_wit_compiled {
     std::vector<u32> stream;
     std::vector<glp_wit_run> runs;
     std::vector<u32> level_run;
+    std::vector<u32> part_level;          // parts + 1 entries: part s owns levels [part_level[s], part_level[s + 1]); a plain plan is ONE part
+    std::vector<glp_wit_part> parts;
     std::vector<u64> dict;
     std::vector<u32> eq;
     std::vector<u32> zero;
@@ -157,29 +169,58 @@ struct glp_wit_compiled {
         return glp_wit_view{stream.data(), runs.data(), level_run.data(), dict.data(), eq.data(), zero.data(), depth, (u32)(eq.size() / 2), n_inputs, n_values,
                             (u32)zero.size()};
     }
-    size_t stream_bytes() const { return stream.size() * 4 + runs.size() * sizeof(glp_wit_run) + level_run.size() * 4 + dict.size() * 8 + (eq.size() + zero.size()) * 4; }
+    size_t stream_bytes() const {
+        return stream.size() * 4 + runs.size() * sizeof(glp_wit_run) + level_run.size() * 4 + dict.size() * 8 + (eq.size() + zero.size()) * 4 +
+               (parts.size() > 1 ? part_level.size() * 4 : 0);
+    }
 };
 
 // program -> schedule.  GLP_E_INVALID for a program witness_run would refuse on structure (or one that reads a variable nobody wrote / writes one
 // twice: witness_run checks those for the segments of glp_witness_eval_mt), GLP_E_UNSUPPORTED when an index does not fit 32 bits.
-inline int glp_wit_compile(const u64* prog, size_t prog_words, size_t n_inputs, size_t n_values, const u64* eq_pairs, size_t n_eq, glp_wit_compiled& out) {
+// seg_bounds / n_seg: the independent segments (see PARTS above); n_seg < 2 compiles the plain plan — one part, seg_bounds not looked at.  With
+// segments also GLP_E_INVALID for an offset that is not an op boundary, descending or past the program, and for a false independence claim.
+inline int glp_wit_compile_ex(const u64* prog, size_t prog_words, size_t n_inputs, size_t n_values, const u64* eq_pairs, size_t n_eq,
+                              const u64* seg_bounds, size_t n_seg, glp_wit_compiled& out) {
     if ((!prog && prog_words) || (!eq_pairs && n_eq)) return GLP_E_INVALID;
     if (n_values >= 0xFFFFFFFFull || n_inputs >= 0xFFFFFFFFull || n_eq >= 0x7FFFFFFFull) return GLP_E_UNSUPPORTED;
+    if (n_seg < 2) n_seg = 0;
+    if (n_seg) {
+        if (!seg_bounds || n_seg >= 0xFFFE) return GLP_E_INVALID;
+        for (size_t k = 0; k <= n_seg; k++)
+            if (seg_bounds[k] > prog_words || (k && seg_bounds[k] < seg_bounds[k - 1])) return GLP_E_INVALID;
+    }
+    const u32 n_parts = n_seg ? (u32)n_seg + 2 : 1;
     const u32 NONE = 0xFFFFFFFFu;
-    std::vector<u32> lvl(n_values, NONE);                      // level of the op that wrote the variable
-    struct Op { u64 pc; u32 level; u32 kind; };
+    std::vector<u32> lvl(n_values, NONE);                      // level, inside its part, of the op that wrote the variable
+    std::vector<uint16_t> owner(n_seg ? n_values : 0, 0);      // ... and that part
+    struct Op { u64 pc; u32 level; u32 kind; };                // level: inside the part while scanning, in the whole schedule afterwards
     std::vector<Op> ops;
     ops.reserve(prog_words / 7 + 1);
-    u32 depth = 0;
+    std::vector<u32> part_ops(n_parts + 1, 0);                 // part s = ops [part_ops[s], part_ops[s + 1])
+    std::vector<u32> part_depth(n_parts, 0);
+    u32 part = 0;
+    size_t bound = 0;                                          // seg_bounds[bound] is the next offset the scan has to land on
     size_t pc = 0;
-    while (pc < prog_words) {
+    for (;;) {
+        while (n_seg && bound <= n_seg && seg_bounds[bound] == pc) {      // (an empty segment: two offsets at one op boundary)
+            part_ops[++part] = (u32)ops.size();
+            bound++;
+        }
+        if (pc >= prog_words) break;
+        if (n_seg && bound <= n_seg && seg_bounds[bound] < pc) return GLP_E_INVALID;          // an offset inside the op just scanned
         const u64 kind = prog[pc];
         if (kind >= GLP_WIT_KINDS || pc + GLP_WIT_OP_LEN[kind] > prog_words) return GLP_E_INVALID;
+        if (ops.size() >= 0xFFFFFFFEull) return GLP_E_UNSUPPORTED;
         const u64* a = prog + pc + 1;
         u32 level = 0;
         bool ok = true;
+        const bool in_segment = n_seg && part >= 1 && part <= n_seg;
         auto rd = [&](u64 var) {                               // an operand: in range and written by an earlier op
             if (var >= n_values || lvl[var] == NONE) { ok = false; return; }
+            if (n_seg && owner[var] != part) {                 // an earlier part's: there before this part starts — unless it is ANOTHER SEGMENT's
+                if (in_segment && owner[var] != 0) ok = false;
+                return;
+            }
             if (lvl[var] + 1 > level) level = lvl[var] + 1;
         };
         u64 wr[GLP_NNF_OUT];
@@ -210,20 +251,35 @@ inline int glp_wit_compile(const u64* prog, size_t prog_words, size_t n_inputs, 
         for (int i = 0; i < n_wr; i++) {
             if (wr[i] >= n_values || lvl[wr[i]] != NONE) return GLP_E_INVALID;      // out of range, or written twice (by another op or by this one)
             lvl[wr[i]] = level;
+            if (n_seg) owner[wr[i]] = (uint16_t)part;
         }
         ops.push_back(Op{pc, level, (u32)kind});
-        if (level + 1 > depth) depth = level + 1;
+        if (level + 1 > part_depth[part]) part_depth[part] = level + 1;
         pc += GLP_WIT_OP_LEN[kind];
     }
+    if (n_seg && bound <= n_seg) return GLP_E_INVALID;          // an offset inside the last op
+    for (u32 s = part + 1; s <= n_parts; s++) part_ops[s] = (u32)ops.size();
     for (size_t k = 0; k < 2 * n_eq; k++) if (eq_pairs[k] >= n_values) return GLP_E_INVALID;
+    // the parts' levels one after the other
+    std::vector<u32> part_level(n_parts + 1, 0);
+    for (u32 s = 0; s < n_parts; s++) {
+        if ((u64)part_level[s] + part_depth[s] >= NONE) return GLP_E_UNSUPPORTED;
+        part_level[s + 1] = part_level[s] + part_depth[s];
+        for (u32 k = part_ops[s]; k < part_ops[s + 1]; k++) ops[k].level += part_level[s];
+    }
+    const u32 depth = part_level[n_parts];
     // counting sort by (level, kind), program order kept inside a run
     std::vector<u64> start((size_t)depth * GLP_WIT_KINDS + 1, 0);
     for (const Op& o : ops) start[(size_t)o.level * GLP_WIT_KINDS + o.kind + 1]++;
     u64 words = 0;
     out = glp_wit_compiled();
     out.level_run.assign((size_t)depth + 1, 0);
+    out.parts.resize(n_parts);
+    for (u32 s = 0; s < n_parts; s++) out.parts[s] = glp_wit_part{(u64)part_ops[s + 1] - part_ops[s], 0, part_depth[s]};
     std::vector<u64> word_at((size_t)depth * GLP_WIT_KINDS, 0);
+    u32 cur = 0;
     for (u32 l = 0; l < depth; l++) {
+        while (part_level[cur + 1] <= l) cur++;
         out.level_run[l] = (u32)out.runs.size();
         u64 width = 0;
         for (u32 k = 0; k < GLP_WIT_KINDS; k++) {
@@ -235,6 +291,7 @@ inline int glp_wit_compile(const u64* prog, size_t prog_words, size_t n_inputs, 
             words += cnt * glp_wit_rec_len(k);
             width += cnt;
         }
+        out.parts[cur].steps += (width + GLP_WIT_WG - 1) / GLP_WIT_WG;
         out.steps += (width + GLP_WIT_WG - 1) / GLP_WIT_WG;
     }
     if (words > 0xFFFFFFFFull) return GLP_E_UNSUPPORTED;
@@ -263,11 +320,15 @@ inline int glp_wit_compile(const u64* prog, size_t prog_words, size_t n_inputs, 
     for (size_t i = 0; i < n_values; i++) if (lvl[i] == NONE) out.zero.push_back((u32)i);
     out.eq.resize(2 * n_eq);
     for (size_t k = 0; k < 2 * n_eq; k++) out.eq[k] = (u32)eq_pairs[k];
+    out.part_level = part_level;
     out.n_ops = ops.size();
     out.depth = depth;
     out.n_inputs = (u32)n_inputs;
     out.n_values = (u32)n_values;
     return GLP_OK;
+}
+inline int glp_wit_compile(const u64* prog, size_t prog_words, size_t n_inputs, size_t n_values, const u64* eq_pairs, size_t n_eq, glp_wit_compiled& out) {
+    return glp_wit_compile_ex(prog, prog_words, n_inputs, n_values, eq_pairs, n_eq, nullptr, 0, out);
 }
 
 // the REORDERED stream, serially, on the host: the check of the schedule on a machine without a GPU (not a product path).  Stops at the first
@@ -288,4 +349,42 @@ inline int glp_wit_run_host(const glp_wit_view& p, const GlpPoseidonConsts& pk, 
     for (u32 k = 0; k < p.n_eq; k++)
         if (values[p.eq[2 * k]] != values[p.eq[2 * k + 1]]) { if (first_bad) *first_bad = k; return GLP_E_REJECT; }
     return GLP_OK;
+}
+
+// WORD CHECKS: the facts a recorded circuit ties between words of its inputs that are NOT program inputs and variables it computes (the
+// wc_var / wc_bits tables of WitnessProgram.check_words).  Check k < n_var: v[var_idx[k]] is the wanted word; check n_var + j: the bits
+// v[bit_vars[i]], i in [bit_start[j], bit_start[j + 1]), packed little-endian (the sum of v << position, mod 2^64) are the wanted word.
+// var_want / bit_want are the instance's n_var / n_bits wanted words.  A variable index >= row_words, the words of an instance's row (no table a
+// recording makes holds one), fails the check instead of being read.
+struct glp_wit_words {
+    const u32* var_idx;
+    const u32* bit_vars;
+    const u32* bit_start;         // n_bits + 1 ascending entries
+    u32 n_var, n_bits;
+};
+GL_HD bool glp_wit_word_ok(const glp_wit_words& t, const u64* v, u64 row_words, const u64* var_want, const u64* bit_want, u32 k) {
+    if (k < t.n_var) return t.var_idx[k] < row_words && v[t.var_idx[k]] == var_want[k];
+    const u32 j = k - t.n_var;
+    u64 packed = 0;
+    for (u32 i = t.bit_start[j]; i < t.bit_start[j + 1]; i++) {
+        if (t.bit_vars[i] >= row_words) return false;
+        const u32 sh = i - t.bit_start[j];
+        packed += sh < 64 ? v[t.bit_vars[i]] << sh : 0;
+    }
+    return packed == bit_want[j];
+}
+// every check of B instances, serially on the host: the lowest failing index of each kind per instance, ~0 when none fails
+inline void glp_wit_check_words_host(const glp_wit_words& t, const u64* values, size_t value_stride, u32 B, const u64* var_want, const u64* bit_want,
+                                     u64* first_bad_var, u64* first_bad_bits) {
+    for (u32 b = 0; b < B; b++) {
+        first_bad_var[b] = first_bad_bits[b] = ~0ull;
+        const u64* v = values + (size_t)b * value_stride;
+        const u64 *vw = var_want + (size_t)b * t.n_var, *bw = bit_want + (size_t)b * t.n_bits;
+        for (u32 k = 0; k < t.n_var + t.n_bits; k++)
+            if (!glp_wit_word_ok(t, v, value_stride, vw, bw, k)) {
+                u64& first = k < t.n_var ? first_bad_var[b] : first_bad_bits[b];
+                const u64 idx = k < t.n_var ? k : k - t.n_var;
+                if (idx < first) first = idx;
+            }
+    }
 }

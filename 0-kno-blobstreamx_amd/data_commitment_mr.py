@@ -93,7 +93,9 @@ class DataCommitmentMapReduce:
         """map_provers: further Provers on the same GPU (their Poseidon constants set): the Map step then proves leaves on all of them at once,
         one host thread each (the latency-bound phases of one leaf proof overlap the throughput-bound phases of another, as in mapreduce.py).
         device_witness (default off: the host evaluator pool): the Map step evaluates the leaves' witness programs ON THE DEVICE, device_witness_chunk
-        leaves per launch (WitnessProgram.evaluate_device; 32 signature leaves are a 340 MB slab), and the provers place and prove from the slab."""
+        leaves per launch (WitnessProgram.evaluate_device; 32 signature leaves are a 340 MB slab), and the provers place and prove from the slab.
+        The Reduce step does the same with the nodes of a level (RecursionProgram.witness_batch: the segmented plan and the word checks on the
+        device), so that no host evaluator runs anywhere."""
         assert leaf_blocks >= 1 and leaf_blocks & (leaf_blocks - 1) == 0 and fan_in >= 2 and fan_in & (fan_in - 1) == 0
         self.prover, self.consts = prover, tuple(np.ascontiguousarray(a, dtype=np.uint64) for a in poseidon_consts)
         self.map_provers, self.map_circuits = list(map_provers), []
@@ -247,7 +249,10 @@ class DataCommitmentMapReduce:
             t0 = time.perf_counter()
             rp = self._node(level, cur[:fan], key, span)
             groups = [cur[k:k + fan] for k in range(0, len(cur), fan)]
-            if len(groups) > 1 and self.map_provers:
+            if getattr(self, "device_witness", False):
+                done = self._reduce_level_device(rp, groups)
+                nxt, public = [d[0] for d in done], done[-1][1]
+            elif len(groups) > 1 and self.map_provers:
                 # several nodes of one level: one host thread per prover, each with its own commitment of the level's (shared) recording
                 from concurrent.futures import ThreadPoolExecutor
                 if id(rp) not in self.node_replicas:
@@ -278,6 +283,49 @@ class DataCommitmentMapReduce:
                 self.last_span = span
                 return nxt[0], public, key, level
             cur = nxt
+
+    def _reduce_level_device(self, rp, groups):
+        """the nodes of one level with their witnesses made on the device: device_witness_chunk groups at a time through rp.witness_batch on the
+        main prover (which returns with its stream synchronised), then every prover — the main one and, for several groups, rp's replicas on the
+        map provers — places and proves its share of the chunk from the slab, as _map_inputs_device does for leaves.  [(proof, public)] in order."""
+        from concurrent.futures import ThreadPoolExecutor
+        workers = [rp]
+        if len(groups) > 1 and self.map_provers:
+            if id(rp) not in self.node_replicas:
+                self.node_replicas[id(rp)] = [rp.replicate(p) for p in self.map_provers]
+            workers += self.node_replicas[id(rp)]
+        n_workers, chunk = len(workers), self.device_witness_chunk
+        out = [None] * len(groups)
+        pool = ThreadPoolExecutor(n_workers - 1) if n_workers > 1 else None
+        try:
+            for lo in range(0, len(groups), chunk):
+                part = groups[lo:lo + chunk]
+                try:
+                    slab = rp.witness_batch(part)
+                except ValueError as e:
+                    msg = str(e)
+                    if msg.startswith("instance "):
+                        k, rest = msg[len("instance "):].split(":", 1)
+                        msg = f"instance {lo + int(k)}:{rest}"
+                    raise ValueError(msg) from None
+
+                def work(w, lo=lo, part=part, slab=slab):
+                    if w:
+                        self.map_provers[w - 1].bind_thread()
+                    for i in range(w, len(part), n_workers):
+                        dw, public = slab.device_witness(workers[w].prover, i, reuse=True)
+                        out[lo + i] = (workers[w].circuit.prove_(dw, self.nq, self.pw, public=public), public)
+                if pool is None:
+                    work(0)
+                else:
+                    futs = [pool.submit(work, w) for w in range(1, n_workers)]
+                    work(0)
+                    for f in futs:
+                        f.result()
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True)
+        return out
 
     def prove_range_distributed(self, heights, data_roots, device=None, comm=None):
         """the same proof with the work spread over the ranks (mapreduce.reduce_tree_distributed): rank r proves the leaves of the r-th CONTIGUOUS

@@ -827,24 +827,50 @@ class WitnessProgram:
             raise ValueError("witness program or inputs malformed")
         return vals
 
-    def plan(self):
+    def plan(self, segments=False):
         """the program compiled into a level schedule (glp_witness_plan_create; cached, not part of save / load: rebuilt on demand).  Host work,
-        no GPU.  The plan — and the copy of it a device holds after the first evaluate_device there — lives as long as this object."""
+        no GPU.  The plan — and the copy of it a device holds after the first evaluate_device there — lives as long as this object.
+        segments=True: the SEGMENTED plan of a program recorded with begin_segment / end_segment (glp_witness_plan_create_ex over seg_bounds: a
+        level schedule per part, a workgroup per segment on the device); cached separately.  A program without segments has only the plain plan."""
         import ctypes
         import weakref
-        pl = self.__dict__.get("_plan")
+        sb = self.seg_bounds if segments else None
+        slot = "_plan" if sb is None else "_plan_seg"
+        pl = self.__dict__.get(slot)
         if pl is None:
             from . import load_library
             lib = load_library()
             h = ctypes.c_void_p()
-            rc = lib.glp_witness_plan_create(self.prog.ctypes.data, self.prog.size, self.n_inputs, self.n_values,
-                                             self.eq_pairs.ctypes.data if self.eq_pairs.size else None, self.eq_pairs.size // 2, ctypes.byref(h))
+            eq = self.eq_pairs.ctypes.data if self.eq_pairs.size else None
+            if sb is None:
+                rc = lib.glp_witness_plan_create(self.prog.ctypes.data, self.prog.size, self.n_inputs, self.n_values, eq, self.eq_pairs.size // 2,
+                                                 ctypes.byref(h))
+            else:
+                sb = np.ascontiguousarray(sb, dtype=np.uint64)
+                rc = lib.glp_witness_plan_create_ex(self.prog.ctypes.data, self.prog.size, self.n_inputs, self.n_values, eq, self.eq_pairs.size // 2,
+                                                    sb.ctypes.data, sb.size - 1, ctypes.byref(h))
             if rc != 0:
                 raise ValueError("witness program malformed" if rc == -1 else f"glp_witness_plan_create: {rc}")
-            pl = self._plan = h.value
-            self._plan_finalizer = weakref.finalize(self, lib.glp_witness_plan_destroy, ctypes.c_void_p(pl))
-            self._plan_finalizer.atexit = False          # at interpreter exit the driver frees the device copy; the HIP runtime may be gone by then
+            pl = h.value
+            setattr(self, slot, pl)
+            fin = weakref.finalize(self, lib.glp_witness_plan_destroy, ctypes.c_void_p(pl))
+            fin.atexit = False          # at interpreter exit the driver frees the device copy; the HIP runtime may be gone by then
+            setattr(self, slot + "_finalizer", fin)
         return pl
+
+    def plan_parts(self, segments=True):
+        """[{'ops', 'depth', 'steps'}] per part of the plan (glp_witness_plan_parts): prefix, each segment, tail — one entry for a plain plan"""
+        import ctypes
+        from . import load_library
+        lib, pl = load_library(), self.plan(segments)
+        n = ctypes.c_uint32(0)
+        rc = lib.glp_witness_plan_parts(pl, ctypes.byref(n), None, None, None)
+        arr = [np.zeros(n.value, dtype=np.uint64) for _ in range(3)]
+        if rc == 0:
+            rc = lib.glp_witness_plan_parts(pl, ctypes.byref(n), *(a.ctypes.data for a in arr))
+        if rc != 0:
+            raise ValueError(f"glp_witness_plan_parts: {rc}")
+        return [dict(zip(("ops", "depth", "steps"), (int(a[k]) for a in arr))) for k in range(n.value)]
 
     def plan_stats(self):
         """{'ops', 'depth', 'steps', 'stream_bytes'} of the level schedule: steps = barrier-separated passes of the kernel's workgroup"""
@@ -856,10 +882,11 @@ class WitnessProgram:
             raise ValueError(f"glp_witness_plan_stats: {rc}")
         return dict(zip(("ops", "depth", "steps", "stream_bytes"), (int(x.value) for x in v)))
 
-    def evaluate_device(self, prover, inputs_batch, slab=None):
+    def evaluate_device(self, prover, inputs_batch, slab=None, segments=False):
         """every variable of B input vectors computed ON THE DEVICE (glp_witness_eval_device: one workgroup per instance, level by level):
         returns a DeviceWitnessBatch owning the [B][n_values + fixed] slab.  ValueError with evaluate's texts (naming the instance) when an
-        instance is refused.  slab: a DeviceWitnessBatch of an earlier call to reuse (same prover, at least as many rows)."""
+        instance is refused.  slab: a DeviceWitnessBatch of an earlier call to reuse (same prover, at least as many rows).
+        segments=True: through the segmented plan — a workgroup per (instance, recorded segment), for recursion nodes; same values and verdicts."""
         import ctypes
         inp = np.ascontiguousarray(inputs_batch, dtype=np.uint64)
         if inp.ndim == 1:
@@ -867,7 +894,7 @@ class WitnessProgram:
         if inp.ndim != 2 or inp.shape[1] != self.n_inputs:
             raise ValueError(f"{inp.shape[-1] if inp.ndim else 0} inputs given, the program takes {self.n_inputs}")
         B = inp.shape[0]
-        plan = self.plan()
+        plan = self.plan(segments)
         if slab is None or slab.prover is not prover or slab.rows < B or slab.program is not self or slab.buf.ptr is None:
             slab = DeviceWitnessBatch(self, prover, B)
         slab.B = B
@@ -934,6 +961,71 @@ class WitnessProgram:
             if bad.size:
                 raise ValueError(f"input {int(k[bad[0]])}: word {int(pos[bad[0]])} differs from the index the transcript derives")
 
+    def _word_tables(self, prover):
+        """the wc_var / wc_bits tables as glp_witness_check_words takes them, resident per prover (checked once: every index a variable, 1..64
+        bits per packed word)"""
+        t = self.__dict__.setdefault("_wc_dev", {}).get(id(prover))
+        if t is None or t["prover"] is not prover or any(b.ptr is None for b in t["bufs"]):
+            nb = self.wc_bits[:, 2].astype(np.int64)
+            var, bit_vars = self.wc_var[:, 2].astype(np.int64), self.wc_bit_vars.astype(np.int64)
+            if ((var.size and (var.min() < 0 or var.max() >= self.n_values)) or (bit_vars.size and (bit_vars.min() < 0 or bit_vars.max() >= self.n_values))
+                    or (nb.size and (nb.min() < 1 or nb.max() > 64)) or int(nb.sum()) != bit_vars.size):
+                raise ValueError("not a recorded circuit of this format")
+            start = np.concatenate(([0], np.cumsum(nb))).astype(np.uint32)
+            bufs = [prover.to_device(var.astype(np.uint32)), prover.to_device(bit_vars.astype(np.uint32)), prover.to_device(start)]
+            t = self._wc_dev[id(prover)] = {"prover": prover, "bufs": bufs, "want": None}
+        return t
+
+    def check_words_device(self, slab, word_lists_per_instance):
+        """check_words on the rows of a DeviceWitnessBatch, ON THE DEVICE (glp_witness_check_words): only the wanted words are uploaded, the
+        variables stay where they are.  word_lists_per_instance[i]: the word lists instance i was evaluated from.  Raises check_words' own texts
+        (for the lowest instance that fails), prefixed with 'instance i: ' when the batch holds more than one."""
+        B, n_var, n_bits = slab.B, self.wc_var.shape[0], self.wc_bits.shape[0]
+        if len(word_lists_per_instance) != B:
+            raise ValueError(f"{len(word_lists_per_instance)} word lists given for a batch of {B}")
+        if B == 0 or n_var + n_bits == 0:
+            return
+        want = np.empty((B, n_var + n_bits), dtype=np.uint64)
+        for i, lists in enumerate(word_lists_per_instance):
+            ws = [np.frombuffer(bytes(w), dtype="<u8") if isinstance(w, (bytes, bytearray)) else np.asarray(w, dtype=np.uint64) for w in lists]
+            sizes = np.array([w.size for w in ws], dtype=np.int64)
+            off = np.concatenate(([0], np.cumsum(sizes)))[:-1]
+            flat = np.concatenate(ws) if ws else np.zeros(0, dtype=np.uint64)
+            k, pos = np.concatenate((self.wc_var[:, 0], self.wc_bits[:, 0])).astype(np.int64), np.concatenate((self.wc_var[:, 1], self.wc_bits[:, 1])).astype(np.int64)
+            if k.max() >= len(ws) or np.any(pos >= sizes[k]):
+                raise ValueError("an input is shorter than this circuit expects")
+            want[i] = flat[off[k] + pos]
+        prover = slab.prover
+        t = self._word_tables(prover)
+        # [B][n_var] then [B][n_bits]
+        packed = np.concatenate((np.ascontiguousarray(want[:, :n_var]).ravel(), np.ascontiguousarray(want[:, n_var:]).ravel()))
+        if t["want"] is None or t["want"].ptr is None or t["want"].nbytes < packed.nbytes:
+            if t["want"] is not None and t["want"].ptr is not None:
+                t["want"].free()
+            t["want"] = DeviceBuffer(prover, packed.nbytes)
+        t["want"].upload(packed)
+        bad_var, bad_bits = np.zeros(B, dtype=np.uint64), np.zeros(B, dtype=np.uint64)
+        d_var, d_bit_vars, d_start = (b.ptr for b in t["bufs"])
+        prover._chk(prover.lib.glp_witness_check_words(prover.ctx, slab.buf.ptr, slab.stride, B, d_var, t["want"].ptr, n_var, d_bit_vars, d_start,
+                                                       t["want"].ptr + B * n_var * 8, n_bits, bad_var.ctypes.data, bad_bits.ctypes.data),
+                    "glp_witness_check_words")
+        for i in range(B):
+            what = self.word_check_refusal(int(bad_var[i]), int(bad_bits[i]))
+            if what is not None:
+                raise ValueError((f"instance {i}: " if B > 1 else "") + what)
+
+    def word_check_refusal(self, bad_var, bad_bits):
+        """check_words' text for the verdict of glp_witness_check_words on one instance (the lowest failing wc_var / wc_bits index, 2^64 - 1 for
+        none): the copies are looked at before the indices, as there.  None when every check holds."""
+        NONE = 0xFFFFFFFFFFFFFFFF
+        if bad_var != NONE:
+            k, pos = self.wc_var[bad_var, :2]
+            return f"input {int(k)}: word {int(pos)} differs from the value the circuit derives"
+        if bad_bits != NONE:
+            k, pos = self.wc_bits[bad_bits, :2]
+            return f"input {int(k)}: word {int(pos)} differs from the index the transcript derives"
+        return None
+
     def _resident(self, prover):
         """what stays on the device per prover: the cell -> variable map, the Poseidon / SHA row lists, an upload buffer for the variables and
         (reuse=True) the wire matrix itself — hipMalloc / hipFree synchronise the WHOLE device, so a witness per proof must not allocate (three
@@ -976,6 +1068,12 @@ class WitnessProgram:
         """free what is resident (for one prover, or all)"""
         for key in [k for k in self._dev if prover is None or k == id(prover)]:
             for buf in self._dev.pop(key).values():
+                if buf is not None and buf.ptr is not None and getattr(buf.prover, "ctx", None):
+                    buf.free()
+        wc = self.__dict__.get("_wc_dev", {})
+        for key in [k for k in wc if prover is None or k == id(prover)]:
+            t = wc.pop(key)
+            for buf in t["bufs"] + [t["want"]]:
                 if buf is not None and buf.ptr is not None and getattr(buf.prover, "ctx", None):
                     buf.free()
 

@@ -201,7 +201,7 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
                                                 builder_wires=SHA_GATE_WIRES, specs=[spec] * len(nodes))
             self.record_seconds[f"padded_root_{len(nodes)}_of_{total_groups}"] = round(time.perf_counter() - t0, 3)
         rp = self.nodes[k]
-        proof, public = rp.prove(nodes, self.nq, self.pw)
+        proof, public = rp.prove(nodes, self.nq, self.pw, device_witness=getattr(self, "device_witness", False))
         if timings is not None:
             timings.append({"level": level, "nodes": 1, "fan_in": len(nodes), "constant_groups": total_groups - len(nodes), "rows": rp.stats["rows"],
                             "seconds_including_first_recording": round(time.perf_counter() - t0, 4)})

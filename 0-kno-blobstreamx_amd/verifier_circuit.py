@@ -759,11 +759,43 @@ class RecursionProgram:
         self.program.check_words(vals, ws)
         return self.program.device_witness(self.prover, vals, reuse=reuse)
 
-    def prove(self, proofs, num_queries=28, pow_bits=16):
-        """(root proof, public inputs) for a batch of proofs of the leaf circuit"""
-        dw, public = self.witness(proofs, reuse=True)
+    def witness_batch(self, groups):
+        """the variables of SEVERAL batches (one list of proofs each: the nodes of a Reduce level) computed ON THE DEVICE, no host evaluator:
+        the inputs from the proofs' words (host numpy; also the words the statement shape fixes), the segmented plan — a workgroup per
+        (batch, child) — then the word checks on the device.  Returns a DeviceWitnessBatch on this program's prover, owned by this object
+        (valid until the next call; freed by free()); device_witness(prover, i) places batch i.  A refused child raises witness()'s ValueError,
+        prefixed with 'instance i: ' when there are several batches."""
+        rows, words = [], []
+        for proofs in groups:
+            inputs, ws = self.program.inputs_from_words(proofs)
+            rows.append(inputs)
+            words.append(ws)
+        old = self.__dict__.get("_slab")
+        try:
+            slab = self.program.evaluate_device(self.prover, np.array(rows, dtype=np.uint64).reshape(len(rows), self.program.n_inputs), slab=old,
+                                                segments=True)
+        except ValueError as e:
+            if len(groups) == 1 and str(e).startswith("instance 0: "):
+                raise ValueError(str(e)[len("instance 0: "):]) from None
+            raise
+        if old is not None and old is not slab:
+            old.free()
+        self._slab = slab
+        self.program.check_words_device(slab, words)
+        return slab
+
+    def prove(self, proofs, num_queries=28, pow_bits=16, device_witness=False):
+        """(root proof, public inputs) for a batch of proofs of the leaf circuit.  device_witness: the witness through witness_batch (evaluated
+        and checked on the device) instead of the host evaluator: the same proof."""
+        if device_witness:
+            dw, public = self.witness_batch([proofs]).device_witness(self.prover, 0, reuse=True)
+        else:
+            dw, public = self.witness(proofs, reuse=True)
         return self.circuit.prove_(dw, num_queries, pow_bits, public=public), public
 
     def free(self):
+        slab = self.__dict__.pop("_slab", None)
+        if slab is not None:
+            slab.free()
         self.program.release(self.prover)
         self.circuit.free()

@@ -347,6 +347,31 @@ int glp_witness_plan_run_host(const glp_witness_plan* plan, const uint64_t* h_rc
  * the plan: shared by every ctx of that device, freed by glp_witness_plan_destroy (not by glp_destroy). */
 int glp_witness_eval_device(glp_ctx* ctx, const glp_witness_plan* plan, const uint64_t* d_inputs, uint64_t* d_values, size_t value_stride,
                             uint32_t B, int32_t* h_status, uint64_t* h_first_bad);
+/* A SEGMENTED plan, for a program that is ONE instance of n_seg mutually independent segments (a recursion node: the verifier sub-circuits of
+ * its children).  seg_bounds: the n_seg + 1 offsets of glp_witness_eval_mt.  The plan has n_seg + 2 PARTS — the prefix [0, seg_bounds[0]), the
+ * segments, the tail — each with a level schedule of its own (a level counts only producers inside the part).  Everything is checked here:
+ * GLP_E_INVALID for an offset that is not an op boundary, descending or past the program, and for a segment that reads what another segment
+ * wrote, besides what glp_witness_plan_create refuses.  n_seg < 2 (seg_bounds then ignored) is glp_witness_plan_create: one part.
+ * glp_witness_eval_device on a segmented plan issues three launches on the ctx's stream — the prefix, all segments at once (a workgroup per
+ * (instance, segment) pair), the tail with the copy constraints — with the verdicts of the plain plan; glp_witness_plan_run_host runs the
+ * parts in order; glp_witness_plan_stats counts depth and steps over all parts. */
+int glp_witness_plan_create_ex(const uint64_t* prog, size_t prog_words, size_t n_inputs, size_t n_values, const uint64_t* eq_pairs, size_t n_eq,
+                               const uint64_t* seg_bounds, size_t n_seg, glp_witness_plan** plan);
+/* per part: ops, levels, steps at 256 lanes.  In: *n_parts = the capacity of the arrays (any of them may be NULL); out: the plan's number of
+ * parts (1 for a plain plan), of which min(capacity, parts) entries were written. */
+int glp_witness_plan_parts(const glp_witness_plan* plan, uint32_t* n_parts, uint64_t* ops, uint64_t* depth, uint64_t* steps);
+/* The word checks of a recorded circuit on evaluated instances ON THE DEVICE (d_values as glp_witness_eval_device leaves them): check k < n_var
+ * of instance b holds when d_values[b][d_var_idx[k]] == d_var_want[b * n_var + k]; check j < n_bits when the variables
+ * d_bit_vars[d_bit_start[j] .. d_bit_start[j + 1]) (0 / 1 values, at most 64 of them), packed little-endian mod 2^64, equal
+ * d_bit_want[b * n_bits + j].  h_first_bad_var[b] / h_first_bad_bits[b]: the lowest failing check of each kind, (uint64_t)-1 when none fails.
+ * A variable index >= value_stride fails its check.  d_bit_start holds n_bits + 1 ascending offsets into d_bit_vars (the caller's contract).
+ * Stream-ordered on the ctx's stream, which is synchronised before the call returns.  ..._host: the same checks on host arrays, no GPU. */
+int glp_witness_check_words(glp_ctx* ctx, const uint64_t* d_values, size_t value_stride, uint32_t B, const uint32_t* d_var_idx,
+                            const uint64_t* d_var_want, uint32_t n_var, const uint32_t* d_bit_vars, const uint32_t* d_bit_start,
+                            const uint64_t* d_bit_want, uint32_t n_bits, uint64_t* h_first_bad_var, uint64_t* h_first_bad_bits);
+int glp_witness_check_words_host(const uint64_t* values, size_t value_stride, uint32_t B, const uint32_t* var_idx, const uint64_t* var_want,
+                                 uint32_t n_var, const uint32_t* bit_vars, const uint32_t* bit_start, const uint64_t* bit_want, uint32_t n_bits,
+                                 uint64_t* first_bad_var, uint64_t* first_bad_bits);
 /* the Poseidon permutation on the host: n states of 12 canonical words, in place (same constants arguments as the host verifiers) */
 int glp_poseidon_permute_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, uint64_t* states, size_t n);
 int glp_plonk_proof_digest_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* h_proof,
