@@ -93,6 +93,9 @@ LDE_CASES = [
     # log_n, rate_bits, batch, plan (of the size-n transforms)
     (6, 1, 3, None), (7, 3, 2, None), (10, 3, 3, None), (12, 2, 1, None), (13, 3, 2, None), (14, 1, 3, None),
     (16, 3, 1, "8:4,8:4"), (16, 2, 2, "10:3,6:4"), (18, 1, 1, "6:4,6:4,6:4"), (15, 4, 1, None),
+    # radix-32 work-items under the coset scale (general strip + FINAL_ROWS with 64-bit restaging, single-pass FINAL_ROWS on the 2^10 / 2^11 / 2^12
+    # tiles): the cases of tests/test_gpu_ntt_radix32.py with at most 2^16 output points per polynomial (the larger ones take minutes here)
+    (15, 1, 2, "9:3:5,6:4"), (11, 3, 2, "11:2:5"), (12, 2, 1, "12:1:5"), (10, 3, 3, "10:2:5"),
 ]
 
 

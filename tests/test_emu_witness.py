@@ -120,37 +120,43 @@ def synthetic_program():
     return np.array(prog, dtype=np.uint64), nv[0], np.array(eq, dtype=np.uint64)
 
 
+def synthetic_cases(rng):
+    """(batch, expected verdicts) for synthetic_program(): an accepted base instance, accepted variants, and every way an instance is refused"""
+    base = rand_field(rng, 62)
+    base[12] = 1                                                       # swap bit
+    base[13:28] = rng.integers(0, 1 << 32, 15, dtype=np.uint64)       # SHA words
+    base[61] = (1 << 35) - 1                                           # T1
+    base[28:50] = rng.integers(0, 1 << 24, 22, dtype=np.uint64)       # limbs
+    base[28], base[39] = (1 << 27) - 1, (1 << 28) - 1                  # ... loose ones
+    base[57] = base[56]
+    base[58] = 0                                                       # INV of 0 is 0
+    batch, want = [base.copy()], [0]
+
+    def case(idx, value, rc):
+        v = base.copy()
+        v[idx] = value
+        batch.append(v)
+        want.append(rc)
+    case(12, 0, 0)                       # no swap
+    case(58, 12345, 0)                   # a real inverse
+    case(59, 0, 0); batch[-1][60] = 0    # EINV of 0
+    case(12, 2, -7)                      # swap bit above 1
+    case(13, 1 << 32, -7)                # SHA_E operand above 32 bits
+    case(19, 1 << 40, -7)                # SHA_A operand
+    case(61, 1 << 35, -7)                # T1 above 35 bits
+    case(23, 1 << 32, -7)                # SHA_W operand
+    case(27, 1 << 33, -7)                # ADD32 operand
+    case(30, 1 << 28, -7)                # NNF limb out of range
+    case(57, int(base[56]) ^ 1, -7)      # copy constraint 0 fails
+    case(5, P, -1)                       # an input that is not a field element
+    case(5, P, -1); batch[-1][12] = 2    # ... together with a refused row: the malformed input decides, as on the host (INPUT ops come first)
+    return batch, want
+
+
 def test_emulated_kernel_on_every_op_kind(emu_witness):
     prog, n_values, eq = synthetic_program()
     rng = np.random.default_rng(14)
     for kind in ("small", "big"):
         consts = poseidon_consts(kind)
-        base = rand_field(rng, 62)
-        base[12] = 1                                                       # swap bit
-        base[13:28] = rng.integers(0, 1 << 32, 15, dtype=np.uint64)       # SHA words
-        base[61] = (1 << 35) - 1                                           # T1
-        base[28:50] = rng.integers(0, 1 << 24, 22, dtype=np.uint64)       # limbs
-        base[28], base[39] = (1 << 27) - 1, (1 << 28) - 1                  # ... loose ones
-        base[57] = base[56]
-        base[58] = 0                                                       # INV of 0 is 0
-        batch, want = [base.copy()], [0]
-
-        def case(idx, value, rc):
-            v = base.copy()
-            v[idx] = value
-            batch.append(v)
-            want.append(rc)
-        case(12, 0, 0)                       # no swap
-        case(58, 12345, 0)                   # a real inverse
-        case(59, 0, 0); batch[-1][60] = 0    # EINV of 0
-        case(12, 2, -7)                      # swap bit above 1
-        case(13, 1 << 32, -7)                # SHA_E operand above 32 bits
-        case(19, 1 << 40, -7)                # SHA_A operand
-        case(61, 1 << 35, -7)                # T1 above 35 bits
-        case(23, 1 << 32, -7)                # SHA_W operand
-        case(27, 1 << 33, -7)                # ADD32 operand
-        case(30, 1 << 28, -7)                # NNF limb out of range
-        case(57, int(base[56]) ^ 1, -7)      # copy constraint 0 fails
-        case(5, P, -1)                       # an input that is not a field element
-        case(5, P, -1); batch[-1][12] = 2    # ... together with a refused row: the malformed input decides, as on the host (INPUT ops come first)
+        batch, want = synthetic_cases(rng)
         compare(emu_witness, prog, 62, n_values, eq, consts, batch, 3, want)

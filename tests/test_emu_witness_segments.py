@@ -123,31 +123,37 @@ def segmented_synthetic_program():
     return np.array(prog, dtype=np.uint64), nv[0], np.array(eq, dtype=np.uint64), np.array(cuts, dtype=np.uint64)
 
 
+def segmented_cases(rng):
+    """(batch, expected verdicts) for segmented_synthetic_program(): a refusal in each of the three launches"""
+    base = rand_field(rng, 62)
+    base[12] = 1                                                       # swap bit
+    base[13:28] = rng.integers(0, 1 << 32, 15, dtype=np.uint64)       # SHA words
+    base[61] = (1 << 35) - 1                                           # T1
+    base[28:50] = rng.integers(0, 1 << 24, 22, dtype=np.uint64)       # limbs
+    base[57] = base[56]
+    batch, want = [base.copy()], [0]
+
+    def case(idx, value, rc):
+        v = base.copy()
+        v[idx] = value
+        batch.append(v)
+        want.append(rc)
+    case(12, 0, 0)                       # no swap
+    case(12, 2, -7)                      # segment A refuses a row: swap bit above 1
+    case(27, 1 << 33, -7)                # segment B refuses a row: ADD32 operand
+    case(57, int(base[56]) ^ 1, -7)      # copy constraint 0 fails (the tail's launch)
+    case(5, P, -1)                       # an input that is not a field element (the prefix's launch)
+    case(5, P, -1); batch[-1][12] = 2    # ... together with a refused row in a LATER launch: the malformed input still decides
+    return batch, want
+
+
 @pytest.mark.parametrize("block", [64, 256])
 def test_three_launches_on_every_op_kind(emu_seg, block):
     prog, n_values, eq, seg = segmented_synthetic_program()
     rng = np.random.default_rng(15)
     for kind in ("small", "big"):
         consts = poseidon_consts(kind)
-        base = rand_field(rng, 62)
-        base[12] = 1                                                       # swap bit
-        base[13:28] = rng.integers(0, 1 << 32, 15, dtype=np.uint64)       # SHA words
-        base[61] = (1 << 35) - 1                                           # T1
-        base[28:50] = rng.integers(0, 1 << 24, 22, dtype=np.uint64)       # limbs
-        base[57] = base[56]
-        batch, want = [base.copy()], [0]
-
-        def case(idx, value, rc):
-            v = base.copy()
-            v[idx] = value
-            batch.append(v)
-            want.append(rc)
-        case(12, 0, 0)                       # no swap
-        case(12, 2, -7)                      # segment A refuses a row: swap bit above 1
-        case(27, 1 << 33, -7)                # segment B refuses a row: ADD32 operand
-        case(57, int(base[56]) ^ 1, -7)      # copy constraint 0 fails (the tail's launch)
-        case(5, P, -1)                       # an input that is not a field element (the prefix's launch)
-        case(5, P, -1); batch[-1][12] = 2    # ... together with a refused row in a LATER launch: the malformed input still decides
+        batch, want = segmented_cases(rng)
         compare_seg(emu_seg, prog, 62, n_values, eq, seg, consts, batch, want, grid=3, seg_grid=5, block=block)
 
 

@@ -26,6 +26,15 @@ def setup(prover, oracle):
     return prover, oracle
 
 
+def use_consts(prover, oracle, kind):
+    """the Poseidon constants of `kind` on the prover and on the oracle: "small" = the small-integer MDS (fast kernels), "big" = random 64-bit MDS
+    entries, which only the generic instantiations (glp_quotient_kernel<true, false>, glp_poseidon_gate_fill_kernel<0>) serve"""
+    rc, circ, diag = consts = poseidon_consts(kind)
+    prover.set_poseidon_constants(rc, circ, diag)
+    oracle.orc_poseidon_set_constants(ptr(rc), ptr(circ), ptr(diag))
+    return consts
+
+
 def test_public_inputs_are_a_skip_statement(setup, pkg):
     """a 2^12-row circuit whose public inputs are the packed public values of a light-client skip (trusted block, trusted header
     hash, target block | target header hash, data commitment): proves, verifies, and is REJECTED for any other statement"""
@@ -76,12 +85,22 @@ def test_public_inputs_are_a_skip_statement(setup, pkg):
     ck.free()
 
 
-@pytest.mark.parametrize("log_n,W,R,n_public,n_pos", [(8, 136, 80, 4, 40), (10, 136, 24, 0, 200), (6, 160, 136, 2, 9)])
-def test_poseidon_gate_circuit(setup, pkg, log_n, W, R, n_public, n_pos):
+@pytest.mark.parametrize("log_n,W,R,n_public,n_pos,kind", [pytest.param(8, 136, 80, 4, 40, "small", id="8-136-80-4-40"),
+                                                           pytest.param(10, 136, 24, 0, 200, "small", id="10-136-24-0-200"),
+                                                           pytest.param(6, 160, 136, 2, 9, "small", id="6-160-136-2-9"),
+                                                           pytest.param(6, 160, 136, 2, 9, "big", id="6-160-136-2-9-big")])
+def test_poseidon_gate_circuit(setup, pkg, log_n, W, R, n_public, n_pos, kind):
     """Poseidon rows: the wire values of every row reproduce the permutation (glp_poseidon_permute and the oracle), the product's
-    GPU witness filler rebuilds them from the 12 inputs, and the circuit proves and verifies with both verifiers"""
+    GPU witness filler rebuilds them from the 12 inputs, and the circuit proves and verifies with both verifiers — on the small-integer
+    MDS and (one shape) on random 64-bit MDS entries, which run the generic instantiations of the filler and of the quotient kernel"""
     prover, oracle = setup
-    consts = poseidon_consts("small")
+    try:
+        poseidon_gate_circuit(prover, oracle, pkg, log_n, W, R, n_public, n_pos, use_consts(prover, oracle, kind))
+    finally:
+        use_consts(prover, oracle, "small")
+
+
+def poseidon_gate_circuit(prover, oracle, pkg, log_n, W, R, n_public, n_pos, consts):
     rng = np.random.default_rng(log_n * 1000 + n_pos)
     n = 1 << log_n
     rows = sorted(int(v) for v in rng.choice(np.arange(n_public, n), size=n_pos, replace=False))
@@ -130,10 +149,18 @@ def test_poseidon_gate_circuit(setup, pkg, log_n, W, R, n_public, n_pos):
     ck.free()
 
 
-def test_k7_direct_parity_extended_gates(setup, pkg):
-    """row a7 directly on the GPU for a circuit with every gate kind (small enough for the big-int restatement)"""
+@pytest.mark.parametrize("kind", ["small", "big"])
+def test_k7_direct_parity_extended_gates(setup, pkg, kind):
+    """row a7 directly on the GPU for a circuit with every gate kind (small enough for the big-int restatement), on the small-integer MDS
+    (glp_quotient_kernel<true, true>) and on random 64-bit MDS entries (the generic <true, false>)"""
     prover, oracle = setup
-    consts = poseidon_consts("small")
+    try:
+        k7_direct_parity_extended_gates(prover, oracle, pkg, use_consts(prover, oracle, kind))
+    finally:
+        use_consts(prover, oracle, "small")
+
+
+def k7_direct_parity_extended_gates(prover, oracle, pkg, consts):
     rng = np.random.default_rng(91)
     log_n, W, R, rb = 5, 136, 32, 3
     circ = pref.build_circuit(rng, log_n, W, n_routed=R, n_public=3, poseidon_rows=(4, 5, 20), consts=consts)
@@ -155,6 +182,44 @@ def test_k7_direct_parity_extended_gates(setup, pkg):
 
     L = {name: lde(vals) for name, vals in (("consts", circ["consts"]), ("sigmas", circ["sigmas"]), ("wires", circ["wires"]), ("zs", zs))}
     assert [[int(v) for v in r] for r in got] == pref.ref_quotient(circ, L, beta, gamma, alpha, rb)
+    ck.free()
+
+
+def test_generic_mds_switch_gives_the_same_proof(setup, pkg):
+    """GLP_K7_GENERIC_MDS=1 (read on every call) sends the small-integer constants through the generic-MDS instantiations of the quotient
+    kernel and of the Poseidon-row filler: the same field values by other arithmetic, so the refilled wires, the quotient values and the
+    (deterministic) proof are identical word for word with and without it"""
+    prover, oracle = setup
+    consts = poseidon_consts("small")
+    log_n, W, R, n_public, n_pos = 8, 136, 80, 4, 40
+    rng = np.random.default_rng(log_n * 1000 + n_pos + 1)
+    rows = sorted(int(v) for v in rng.choice(np.arange(n_public, 1 << log_n), size=n_pos, replace=False))
+    circ = pref.build_circuit(rng, log_n, W, n_routed=R, n_public=n_public, poseidon_rows=rows, consts=consts)
+    wires = circ["wires"]
+    blank = wires.copy()
+    blank[12:pref.POS_SWAP, rows] = 0
+    blank[pref.POS_SWAP + 1:pref.POS_WIRES, rows] = 0
+    challenges = [int(v) for v in rand_field(rng, 6)]
+    ck = pkg.PlonkCircuit(prover, circ["consts"], circ["sigmas"], n_wires=W, n_public=n_public, poseidon=True)
+    assert "GLP_K7_GENERIC_MDS" not in os.environ
+    got = {}
+    try:
+        for generic in (False, True):
+            if generic:
+                os.environ["GLP_K7_GENERIC_MDS"] = "1"
+            dw = prover.to_device(blank)
+            prover.poseidon_gate_fill_rows(dw, log_n, W, rows)
+            filled = dw.download(wires.shape)
+            proof = ck.prove_(dw, 10, 6, public=circ["public"])
+            dw.free()
+            got[generic] = (filled, ck.debug_stage(wires, "quotient", challenges, public=circ["public"]), proof)
+    finally:
+        os.environ.pop("GLP_K7_GENERIC_MDS", None)
+    assert np.array_equal(got[False][0], wires) and np.array_equal(got[True][0], wires)
+    assert np.array_equal(got[True][1], got[False][1])
+    assert got[True][2] == got[False][2]
+    assert ck.verify(got[True][2], 10, 6, public=circ["public"]), prover.last_reject
+    pref.verify_plonk(got[True][2], oracle, pos_consts=consts, public=circ["public"])
     ck.free()
 
 

@@ -46,16 +46,38 @@ def test_poseidon_permutation(prover, oracle, kind):
 
 @pytest.mark.parametrize("kind,leaf_len,log_leaves,cap_h", [("small", 135, 12, 4), ("small", 3, 8, 0), ("small", 4, 5, 5),
                                                             ("small", 8, 10, 1), ("small", 9, 6, 6), ("small", 1, 0, 0),
-                                                            ("big", 20, 9, 3), ("small", 16, 14, 4)])
+                                                            ("big", 20, 9, 3), ("small", 16, 14, 4),
+                                                            # 2^16 leaves: the level of 32768 nodes runs glp_merkle_level_kernel (levels of more
+                                                            # than 16384 nodes), 16384 .. 128 the per-level cooperative kernel, then the single-launch
+                                                            # top — on the small-integer and on the generic MDS
+                                                            ("small", 5, 16, 3), ("big", 3, 16, 0)])
 def test_merkle_tree(prover, oracle, kind, leaf_len, log_leaves, cap_h):
     use_consts(prover, oracle, kind)
-    rng = np.random.default_rng(leaf_len * 100 + log_leaves)
-    leaves = rand_field(rng, (1 << log_leaves, leaf_len))
-    dig_ref, cap_ref = oracle_merkle(oracle, leaves, cap_h)
-    dig, cap = prover.merkle_tree(leaves, cap_h)
-    assert np.array_equal(dig, dig_ref) and np.array_equal(cap, cap_ref)
-    dig2, cap2 = prover.merkle_tree(np.ascontiguousarray(leaves.T), cap_h, poly_major=True)
-    assert np.array_equal(dig2, dig_ref) and np.array_equal(cap2, cap_ref)
+    try:
+        rng = np.random.default_rng(leaf_len * 100 + log_leaves)
+        leaves = rand_field(rng, (1 << log_leaves, leaf_len))
+        dig_ref, cap_ref = oracle_merkle(oracle, leaves, cap_h)
+        dig, cap = prover.merkle_tree(leaves, cap_h)
+        assert np.array_equal(dig, dig_ref) and np.array_equal(cap, cap_ref)
+        dig2, cap2 = prover.merkle_tree(np.ascontiguousarray(leaves.T), cap_h, poly_major=True)
+        assert np.array_equal(dig2, dig_ref) and np.array_equal(cap2, cap_ref)
+    finally:
+        use_consts(prover, oracle, "small")
+
+
+def test_merkle_tree_without_the_cooperative_kernels():
+    """GLP_COOP_MAX_NODES=0 (read once per process, hence a child process): every level of every test_merkle_tree case, down to the cap, is
+    built by glp_merkle_level_kernel alone and must give the same digests as the oracle"""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, GLP_COOP_MAX_NODES="0")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider",
+                        "-k", "merkle_tree and not without_the_cooperative"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       cwd=os.path.dirname(here))
+    tail = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "10 passed" in tail and "skipped" not in tail and "failed" not in tail, tail
 
 
 def test_polynomial_batch_from_values(prover, oracle, pkg):

@@ -13,6 +13,8 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import P, poseidon_consts, ptr, rand_field  # noqa: E402
 import __graft_entry__ as graft  # noqa: E402
+from test_emu_witness import synthetic_cases, synthetic_program  # noqa: E402
+from test_emu_witness_segments import segmented_cases, segmented_synthetic_program  # noqa: E402
 
 NONE = (1 << 64) - 1
 
@@ -31,12 +33,17 @@ def host_eval(lib, prog, n_values, eq, consts, inputs):
     return rc, (NONE if bad.value == ctypes.c_size_t(-1).value else bad.value), vals
 
 
-def raw_device_eval(prover, prog, n_inputs, n_values, eq, batch, pad=5):
-    """the C ABI directly: plan, upload, evaluate, download everything"""
+def raw_device_eval(prover, prog, n_inputs, n_values, eq, batch, pad=5, seg=None):
+    """the C ABI directly: plan (segmented when seg holds the segment bounds), upload, evaluate, download everything"""
     lib = prover.lib
     prog, eq = np.ascontiguousarray(prog, dtype=np.uint64), np.ascontiguousarray(eq, dtype=np.uint64)
     h = ctypes.c_void_p()
-    assert lib.glp_witness_plan_create(prog.ctypes.data, prog.size, n_inputs, n_values, eq.ctypes.data if eq.size else None, eq.size // 2, ctypes.byref(h)) == 0
+    if seg is None:
+        assert lib.glp_witness_plan_create(prog.ctypes.data, prog.size, n_inputs, n_values, eq.ctypes.data if eq.size else None, eq.size // 2, ctypes.byref(h)) == 0
+    else:
+        seg = np.ascontiguousarray(seg, dtype=np.uint64)
+        assert lib.glp_witness_plan_create_ex(prog.ctypes.data, prog.size, n_inputs, n_values, eq.ctypes.data if eq.size else None, eq.size // 2,
+                                              seg.ctypes.data, seg.size - 1, ctypes.byref(h)) == 0
     inp = np.ascontiguousarray(batch, dtype=np.uint64).reshape(len(batch), n_inputs)
     B, stride = inp.shape[0], n_values + pad
     d_in = prover.to_device(inp)
@@ -165,6 +172,50 @@ def test_more_instances_than_workgroups(prover):
         rc_h, bad_h, vals_h = host_eval(prover.lib, prog, nv, eq, consts, batch[b])
         assert (int(status[b]), int(bad[b])) == (rc_h, bad_h) == ((-7, 0) if b in broken else (0, NONE))
         assert vals[b].tobytes() == vals_h.tobytes()
+
+
+def check_raw_batch(prover, prog, n_inputs, n_values, eq, consts, batch, want, seg=None):
+    """check_batch for a program given as arrays: verdict, first failing pair, values — instance by instance against glp_witness_eval"""
+    status, bad, vals = raw_device_eval(prover, prog, n_inputs, n_values, eq, batch, seg=seg)
+    for b, inputs in enumerate(batch):
+        rc_h, bad_h, vals_h = host_eval(prover.lib, prog, n_values, eq, consts, inputs)
+        print(f"instance {b}: host ({rc_h}, {bad_h})  device ({int(status[b])}, {int(bad[b])})")
+        assert (int(status[b]), int(bad[b])) == (rc_h, bad_h), f"instance {b}"
+        assert rc_h == want[b], f"instance {b}"
+        if rc_h == 0 or bad_h != NONE:
+            assert vals[b].tobytes() == vals_h.tobytes(), f"instance {b}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["small", "big"])
+def test_every_op_kind_on_both_constant_kinds(prover, kind):
+    """the synthetic program of tests/test_emu_witness.py (every op kind, a 150-wide level, a 40-deep chain) with its thirteen accept / refuse
+    cases through glp_witness_eval_kernel<true> (small-integer MDS) and <false> (generic MDS: any other injected constants)"""
+    consts = poseidon_consts(kind)
+    prog, n_values, eq = synthetic_program()
+    batch, want = synthetic_cases(np.random.default_rng(14))
+    assert len(batch) == 14 and sorted(set(want)) == [-7, -1, 0]
+    prover.set_poseidon_constants(*consts)
+    try:
+        check_raw_batch(prover, prog, 62, n_values, eq, consts, batch, want)
+    finally:
+        prover.set_poseidon_constants(*poseidon_consts("small"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["small", "big"])
+def test_segmented_every_op_kind_on_both_constant_kinds(prover, kind):
+    """the segmented synthetic program of tests/test_emu_witness_segments.py (prefix | two segments | tail, a refusal in each launch) through
+    glp_witness_eval_part_kernel<true> and <false>"""
+    consts = poseidon_consts(kind)
+    prog, n_values, eq, seg = segmented_synthetic_program()
+    batch, want = segmented_cases(np.random.default_rng(15))
+    assert len(batch) == 7 and sorted(set(want)) == [-7, -1, 0]
+    prover.set_poseidon_constants(*consts)
+    try:
+        check_raw_batch(prover, prog, 62, n_values, eq, consts, batch, want, seg=seg)
+    finally:
+        prover.set_poseidon_constants(*poseidon_consts("small"))
 
 
 @pytest.mark.gpu
