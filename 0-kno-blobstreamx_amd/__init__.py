@@ -93,6 +93,7 @@ class FriStatement(ctypes.Structure):
 DEFAULT_MIN_QUERIES = 28
 DEFAULT_MIN_POW_BITS = 16
 DEFAULT_MIN_RATE_BITS = 3
+MERKLE_FUSE_DEFAULT = 0xFFFFFFFF      # glp_merkle_batch: the library's measured fusion threshold (include/glprover.h)
 UNBOUND = "unbound"      # explicit opt-out for plonk_verify*: do not bind the proof to a circuit's verifying key
 
 
@@ -165,6 +166,12 @@ def load_library():
         "glp_merkle": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
         "glp_merkle_from_polys": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.c_uint32, _vp, _vp]),
+        "glp_merkle_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]),
+        "glp_merkle_batch_plan": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                 ctypes.POINTER(ctypes.c_uint32)]),
+        "glp_commit_values_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                   _vp, _vp, ctypes.c_uint64, _vp]),
         "glp_fri_fold2": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp]),
         "glp_sha256_trace": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
         "glp_sha512_trace": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
@@ -644,6 +651,46 @@ class Prover:
         dd.free()
         return dig, cap
 
+    @staticmethod
+    def merkle_batch_plan(log_leaves, cap_h, fuse_max_log=None):
+        """(launches, fused launches) glp_merkle_batch issues for one shape, leaf hashing included (host only)"""
+        n, f = ctypes.c_uint32(), ctypes.c_uint32()
+        rc = load_library().glp_merkle_batch_plan(log_leaves, cap_h, MERKLE_FUSE_DEFAULT if fuse_max_log is None else fuse_max_log,
+                                                  ctypes.byref(n), ctypes.byref(f))
+        if rc != 0:
+            raise GlpError(f"glp_merkle_batch_plan: {_ERR.get(rc, rc)}")
+        return n.value, f.value
+
+    def merkle_batch_(self, d_src, src_tree_stride, leaf_len, log_leaves, cap_h, B, d_digests, digest_tree_stride=None, poly_major=False,
+                      poly_stride=None, fuse_max_log=None, want_caps=True):
+        """B trees of one shape in one call (glp_merkle_batch): strides in u64 words; returns caps [B][2^cap_h][4], or None (and no
+        synchronisation) with want_caps=False"""
+        caps = np.zeros((B, 1 << cap_h, 4), dtype=np.uint64) if want_caps else None
+        self._chk(self.lib.glp_merkle_batch(self.ctx, _ptr(d_src), src_tree_stride, 1 if poly_major else 0,
+                                            (poly_stride or (1 << log_leaves)) if poly_major else 0, leaf_len, log_leaves, cap_h, B,
+                                            MERKLE_FUSE_DEFAULT if fuse_max_log is None else fuse_max_log, _ptr(d_digests),
+                                            self.merkle_digest_len(log_leaves, cap_h) if digest_tree_stride is None else digest_tree_stride,
+                                            caps.ctypes.data if want_caps and B else None), "glp_merkle_batch")
+        return caps
+
+    def merkle_trees(self, leaves, cap_h, poly_major=False, fuse_max_log=None):
+        """the batched twin of merkle_tree: leaves [B][n_leaves][leaf_len] (or, poly_major, [B][leaf_len][n_leaves]) ->
+        (digests [B][*][4], caps [B][2^cap_h][4])"""
+        a = np.ascontiguousarray(leaves, dtype=np.uint64)
+        assert a.ndim == 3
+        B = a.shape[0]
+        n_leaves, leaf_len = (a.shape[2], a.shape[1]) if poly_major else a.shape[1:]
+        log_leaves = n_leaves.bit_length() - 1
+        assert 1 << log_leaves == n_leaves
+        nd = self.merkle_digest_len(log_leaves, cap_h)
+        d = self.to_device(a)
+        dd = self.alloc(max(8, B * nd * 8))
+        caps = self.merkle_batch_(d, n_leaves * leaf_len, leaf_len, log_leaves, cap_h, B, dd, poly_major=poly_major, fuse_max_log=fuse_max_log)
+        dig = dd.download((B, nd // 4, 4))
+        d.free()
+        dd.free()
+        return dig, caps
+
     def fri_fold2(self, evals, shift, beta):
         """evals [n][2] in bit-reversed order over shift*<w_n> -> [n/2][2]"""
         e = np.ascontiguousarray(evals, dtype=np.uint64)
@@ -1048,8 +1095,53 @@ class PolynomialBatch:
         prover.ntt_(d, log_n, n_polys, inverse=True)
         return cls.from_coeffs(prover, d, n_polys, log_n, rate_bits, cap_height)
 
+    @classmethod
+    def from_values_batch(cls, prover, values, rate_bits, cap_height):
+        """values [B][n_polys][n] -> B PolynomialBatch objects committed in ONE call (glp_commit_values_batch: one inverse NTT, one LDE, B
+        Merkle trees built together, one copy of all caps).  The B objects are views: coeffs / lde / digests are integer device addresses
+        into three slabs shared by the whole batch and owned by one holder object (view.slabs; slabs.free() releases them, as closing the
+        prover does); free() on a view releases nothing."""
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        assert v.ndim == 3
+        B, n_polys, n = v.shape
+        log_n = n.bit_length() - 1
+        assert 1 << log_n == n
+        log_N = log_n + rate_bits
+        nd = Prover.merkle_digest_len(log_N, cap_height)
+        slabs = _BatchSlabs(prover.to_device(v), prover.alloc(max(8, B * n_polys * (8 << log_N))), prover.alloc(max(8, B * nd * 8)))
+        caps = np.zeros((B, 1 << cap_height, 4), dtype=np.uint64)
+        try:
+            prover._chk(prover.lib.glp_commit_values_batch(prover.ctx, slabs.coeffs.ptr, n_polys, log_n, rate_bits, cap_height, B, slabs.lde.ptr,
+                                                           slabs.digests.ptr, nd, caps.ctypes.data if B else None), "glp_commit_values_batch")
+        except GlpError:
+            slabs.free()
+            raise
+        out = []
+        for b in range(B):
+            pb = cls(prover, n_polys, log_n, rate_bits, cap_height)
+            pb.slabs = slabs
+            pb.coeffs = slabs.coeffs.ptr + b * n_polys * (8 << log_n)
+            pb.lde = slabs.lde.ptr + b * n_polys * (8 << log_N)
+            pb.digests = slabs.digests.ptr + b * nd * 8
+            pb.cap = caps[b]
+            out.append(pb)
+        return out
+
     def free(self):
         for b in (self.coeffs, self.lde, self.digests):
             if isinstance(b, DeviceBuffer):
+                b.free()
+        self.coeffs = self.lde = self.digests = None
+
+
+class _BatchSlabs:
+    """the three device slabs behind the views of one PolynomialBatch.from_values_batch call"""
+
+    def __init__(self, coeffs, lde, digests):
+        self.coeffs, self.lde, self.digests = coeffs, lde, digests
+
+    def free(self):
+        for b in (self.coeffs, self.lde, self.digests):
+            if b is not None:
                 b.free()
         self.coeffs = self.lde = self.digests = None

@@ -5,6 +5,8 @@
 #include <vector>
 #include "glp_ctx.h"
 #include "hash_kernels.cuh"
+#include "merkle_batch_kernels.cuh"
+#include "merkle_plan.h"
 
 #include "hash_state.h"
 #include "poseidon_precomp.h"
@@ -182,6 +184,96 @@ extern "C" int glp_merkle_from_polys(glp_ctx* c, const uint64_t* d_polys, uint64
                                      uint32_t log_leaves, uint32_t cap_h, uint64_t* d_digests, uint64_t* h_cap) {
     if (c && log_leaves <= 40 && poly_stride < (1ull << log_leaves)) { glp_set_err(c, "glp_merkle_from_polys: stride < leaves"); return GLP_E_INVALID; }
     return merkle_impl(c, d_polys, poly_stride, true, leaf_len, log_leaves, cap_h, d_digests, h_cap);
+}
+
+// ---- B trees of one shape per launch (kernels: merkle_batch_kernels.cuh; plan: merkle_plan.h) -------------------------------------
+extern "C" int glp_merkle_batch_plan(uint32_t log_leaves, uint32_t cap_h, uint32_t fuse_max_log, uint32_t* n_launches, uint32_t* n_fused) {
+    if (log_leaves > 40 || cap_h > log_leaves) return GLP_E_INVALID;
+    std::vector<glp_merkle_step> steps;
+    glp_merkle_plan_steps(log_leaves, cap_h, fuse_max_log, steps);
+    u32 nf = 0;
+    for (const glp_merkle_step& s : steps) nf += s.fused;
+    if (n_launches) *n_launches = 1 + (u32)steps.size();      // the leaf launch
+    if (n_fused) *n_fused = nf;
+    return GLP_OK;
+}
+
+extern "C" int glp_merkle_batch(glp_ctx* c, const uint64_t* d_src, uint64_t src_tree_stride, int poly_major, uint64_t poly_stride,
+                                uint32_t leaf_len, uint32_t log_leaves, uint32_t cap_h, uint32_t B, uint32_t fuse_max_log, uint64_t* d_digests,
+                                uint64_t digest_tree_stride, uint64_t* h_caps) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    if (B == 0) return GLP_OK;
+    if (!d_src || !d_digests) { glp_set_err(c, "glp_merkle_batch: null buffer"); return GLP_E_INVALID; }
+    if (const char* why = glp_merkle_batch_check(src_tree_stride, poly_major, poly_stride, leaf_len, log_leaves, cap_h, digest_tree_stride)) {
+        glp_set_err(c, "glp_merkle_batch: %s", why);
+        return GLP_E_INVALID;
+    }
+    const u64 nl = 1ull << log_leaves;
+    int rc = need_consts(c);
+    if (rc) return rc;
+    glp_hash_state* h = c->hash;
+    const GlpPoseidonConsts k = consts_of(h);
+    std::vector<glp_merkle_step> steps;
+    glp_merkle_plan_steps(log_leaves, cap_h, fuse_max_log, steps);
+    const u64 leaf_bpt = (nl + 255) / 256;
+    u64 max_blocks = leaf_bpt * B;
+    for (const glp_merkle_step& s : steps) if (glp_merkle_step_blocks(s) * B > max_blocks) max_blocks = glp_merkle_step_blocks(s) * B;
+    if (max_blocks > 0x7fffffffull) { glp_set_err(c, "glp_merkle_batch: a launch of %llu workgroups", (unsigned long long)max_blocks); return GLP_E_UNSUPPORTED; }
+    const dim3 blk(256);
+    const u64 stride = poly_major ? poly_stride : (u64)leaf_len;
+    {
+        const dim3 g((unsigned)(leaf_bpt * B));
+        const u32 bpt = (u32)leaf_bpt;
+        if (h->small_mds) {
+            if (poly_major) hipLaunchKernelGGL((glp_hash_leaves_batch_kernel<true, true>), g, blk, 0, c->stream, d_src, src_tree_stride, stride, leaf_len, nl, bpt, d_digests, digest_tree_stride, k);
+            else hipLaunchKernelGGL((glp_hash_leaves_batch_kernel<true, false>), g, blk, 0, c->stream, d_src, src_tree_stride, stride, leaf_len, nl, bpt, d_digests, digest_tree_stride, k);
+        } else {
+            if (poly_major) hipLaunchKernelGGL((glp_hash_leaves_batch_kernel<false, true>), g, blk, 0, c->stream, d_src, src_tree_stride, stride, leaf_len, nl, bpt, d_digests, digest_tree_stride, k);
+            else hipLaunchKernelGGL((glp_hash_leaves_batch_kernel<false, false>), g, blk, 0, c->stream, d_src, src_tree_stride, stride, leaf_len, nl, bpt, d_digests, digest_tree_stride, k);
+        }
+        GLP_HIPCHK(c, hipGetLastError());
+    }
+    for (const glp_merkle_step& s : steps) {
+        const u32 bpt = (u32)glp_merkle_step_blocks(s);
+        const dim3 g((unsigned)((u64)bpt * B));
+        const u64 in_off = glp_merkle_level_offset(log_leaves, s.in_log);
+        if (s.fused) {
+            if (h->small_mds) hipLaunchKernelGGL(glp_merkle_subtree_kernel<true>, g, blk, 0, c->stream, d_digests, digest_tree_stride, in_off, s.in_log, s.s_log, s.n_levels, bpt, k);
+            else hipLaunchKernelGGL(glp_merkle_subtree_kernel<false>, g, blk, 0, c->stream, d_digests, digest_tree_stride, in_off, s.in_log, s.s_log, s.n_levels, bpt, k);
+        } else {
+            const u64 count = 1ull << (s.in_log - 1);
+            if (h->small_mds) hipLaunchKernelGGL(glp_merkle_level_batch_kernel<true>, g, blk, 0, c->stream, d_digests, digest_tree_stride, in_off, count, bpt, k);
+            else hipLaunchKernelGGL(glp_merkle_level_batch_kernel<false>, g, blk, 0, c->stream, d_digests, digest_tree_stride, in_off, count, bpt, k);
+        }
+        GLP_HIPCHK(c, hipGetLastError());
+    }
+    if (h_caps) {     // the B caps sit one digest_tree_stride apart: one strided copy
+        const size_t cap_bytes = (size_t)32 << cap_h;
+        GLP_HIPCHK(c, hipMemcpy2DAsync(h_caps, cap_bytes, d_digests + glp_merkle_level_offset(log_leaves, cap_h), digest_tree_stride * 8, cap_bytes, B,
+                                       hipMemcpyDeviceToHost, c->stream));
+        GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return GLP_OK;
+}
+
+extern "C" int glp_commit_values_batch(glp_ctx* c, uint64_t* d_vals, uint32_t n_polys, uint32_t log_n, uint32_t rate_bits, uint32_t cap_h, uint32_t B,
+                                       uint64_t* d_lde, uint64_t* d_digests, uint64_t digest_tree_stride, uint64_t* h_caps) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    if (B == 0) return GLP_OK;
+    const u32 log_N = log_n + rate_bits;
+    if (!d_vals || !d_lde || !d_digests || n_polys == 0 || log_n > 32 || rate_bits > 8 || cap_h > log_N || (u64)B * n_polys > 0xffffffffull) {
+        glp_set_err(c, "glp_commit_values_batch: bad argument");
+        return GLP_E_INVALID;
+    }
+    const u32 rows = B * n_polys;
+    int rc = glp_ntt(c, d_vals, log_n, rows, 1);
+    if (rc) return rc;
+    rc = glp_lde_coset(c, d_vals, d_lde, log_n, rate_bits, rows, 7, GLP_NTT_BITREV);
+    if (rc) return rc;
+    const u64 N = 1ull << log_N;
+    return glp_merkle_batch(c, d_lde, (u64)n_polys * N, 1, N, n_polys, log_N, cap_h, B, GLP_MERKLE_FUSE_DEFAULT, d_digests, digest_tree_stride, h_caps);
 }
 
 extern "C" int glp_fri_fold2(glp_ctx* c, const uint64_t* d_evals, uint64_t* d_out, uint32_t log_n, uint64_t shift,

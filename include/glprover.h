@@ -127,6 +127,29 @@ int glp_merkle(glp_ctx* ctx, const uint64_t* d_leaves, uint32_t leaf_len, uint32
  * (leaf i = column i), so the LDE output is hashed without a transpose pass */
 int glp_merkle_from_polys(glp_ctx* ctx, const uint64_t* d_polys, uint64_t poly_stride, uint32_t leaf_len,
                           uint32_t log_leaves, uint32_t cap_h, uint64_t* d_digests, uint64_t* h_cap);
+#define GLP_MERKLE_FUSE_DEFAULT 0xFFFFFFFFu
+/* B trees of one shape.  Tree b reads d_src + b * src_tree_stride (u64 words): leaves as glp_merkle (poly_major = 0, poly_stride ignored)
+ * or as glp_merkle_from_polys (poly_major = 1: [leaf_len][poly_stride]); its digests, in the layout of glp_merkle, go to
+ * d_digests + b * digest_tree_stride.  h_caps (may be NULL): [B][4 << cap_h] words, ONE copy, synchronous if given.
+ * fuse_max_log: levels of at most 2^fuse_max_log nodes per tree are built by the fused subtree kernel (up to 9 levels per launch),
+ * wider ones one launch per level; GLP_MERKLE_FUSE_DEFAULT = the library's measured default; 0 = never fuse.
+ * GLP_E_INVALID also for digest_tree_stride < 4 * ((2 << log_leaves) - (1 << cap_h)), a src_tree_stride smaller than one tree's leaves and
+ * poly_major with poly_stride < 2^log_leaves; B == 0 is GLP_OK and does nothing.  Words of a digest block past the tree's length are left
+ * alone.  GLP_COOP_MAX_NODES is not read.
+ * Measured (profiles/merkle_batch.json; 2^19 leaves, cap 4): the default is 15 — 6 launches per CALL where glp_merkle takes 14 launches, a
+ * copy and a synchronise per TREE; 12 - 14 % (144-word leaves) and 33 - 37 % (16-word leaves) less time than B = 4 / 8 sequential
+ * glp_merkle_from_polys calls.  B = 1 gains nothing (+0.5 % and +0.04 %, inside the baseline's run-to-run spread): one tree should keep
+ * calling glp_merkle. */
+int glp_merkle_batch(glp_ctx* ctx, const uint64_t* d_src, uint64_t src_tree_stride, int poly_major, uint64_t poly_stride, uint32_t leaf_len,
+                     uint32_t log_leaves, uint32_t cap_h, uint32_t B, uint32_t fuse_max_log, uint64_t* d_digests,
+                     uint64_t digest_tree_stride, uint64_t* h_caps);
+/* the launches glp_merkle_batch issues for that shape (leaf hashing included); host only, no ctx */
+int glp_merkle_batch_plan(uint32_t log_leaves, uint32_t cap_h, uint32_t fuse_max_log, uint32_t* n_launches, uint32_t* n_fused);
+/* d_vals [B * n_polys][2^log_n]: values in, coefficients out (in place); d_lde [B * n_polys][2^(log_n + rate_bits)], bit-reversed, coset
+ * shift 7 — exactly what commit_values / PolynomialBatch.from_values produce per batch; then glp_merkle_batch over the B LDE blocks
+ * (poly-major, leaf_len = n_polys) at the default fusion. */
+int glp_commit_values_batch(glp_ctx* ctx, uint64_t* d_vals, uint32_t n_polys, uint32_t log_n, uint32_t rate_bits, uint32_t cap_h, uint32_t B,
+                            uint64_t* d_lde, uint64_t* d_digests, uint64_t digest_tree_stride, uint64_t* h_caps);
 
 /* ---- FRI (row a8; upstream name recalled: plonky2::fri::prover) -------------------- */
 /* arity-2 fold of extension-field evaluations in bit-reversed order over shift*<w_{log_n}>:
