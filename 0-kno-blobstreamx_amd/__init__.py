@@ -186,6 +186,14 @@ def load_library():
         "glp_fri_prove": (ctypes.c_int, [_vp, ctypes.POINTER(FriConfig), ctypes.POINTER(FriBatch), ctypes.c_uint32,
                                          ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t)]),
         "glp_free_host": (None, [_vp]),
+        "glp_fri_prove_batch": (ctypes.c_int, [_vp, ctypes.POINTER(FriConfig), ctypes.POINTER(FriBatch), ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t)]),
+        "glp_fri_prove_batch_plan": (ctypes.c_int, [ctypes.POINTER(FriConfig), _vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                    ctypes.POINTER(ctypes.c_uint32)]),
+        "glp_fri_last_batch_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 3),
+        "glp_pow_grind_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+        "glp_fri_fold_layer_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.c_uint64, _vp, ctypes.c_uint32]),
         "glp_plonk_setup": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.POINTER(_vp)]),
         "glp_plonk_free": (None, [_vp]),
@@ -775,6 +783,88 @@ class Prover:
         data = ctypes.string_at(proof.value, ln.value)
         self.lib.glp_free_host(proof)
         return data
+
+    @staticmethod
+    def _fri_config(log_n, rate_bits, cap_height, arity_bits, final_poly_bits, num_queries, pow_bits, shift, point_mults):
+        pm = (ctypes.c_uint64 * 4)(*(list(point_mults) + [0] * (4 - len(point_mults))))
+        return FriConfig(log_n, rate_bits, cap_height, arity_bits, final_poly_bits, num_queries, pow_bits, shift, len(point_mults), pm)
+
+    def fri_prove_batch(self, instances, rate_bits, cap_height, arity_bits=4, final_poly_bits=5, num_queries=28, pow_bits=16,
+                        shift=COSET_SHIFT, point_mults=(1,), open_masks=None):
+        """B opening proofs of one shape in one call (glp_fri_prove_batch).  instances: a list of lists of PolynomialBatch, one inner
+        list per proof (views of from_values_batch and objects of from_values may be mixed, and an object may appear in several
+        instances).  Returns the B proofs, each byte for byte what fri_prove returns for that instance alone."""
+        B = len(instances)
+        if B == 0:
+            return []
+        nb = len(instances[0])
+        log_n = instances[0][0].log_n
+        cfg = self._fri_config(log_n, rate_bits, cap_height, arity_bits, final_poly_bits, num_queries, pow_bits, shift, point_mults)
+        if open_masks is None:
+            open_masks = [(1 << len(point_mults)) - 1] * nb
+        arr = (FriBatch * (B * nb))()
+        keep = []
+        for i, inst in enumerate(instances):
+            assert len(inst) == nb
+            for j, b in enumerate(inst):
+                assert b.log_n == log_n and b.rate_bits == rate_bits
+                cap = np.ascontiguousarray(b.cap, dtype=np.uint64)
+                keep.append(cap)
+                arr[i * nb + j] = FriBatch(_ptr(b.coeffs), _ptr(b.lde), _ptr(b.digests), cap.ctypes.data, b.n_polys, open_masks[j])
+        proofs = (_vp * B)()
+        lens = (ctypes.c_size_t * B)()
+        self._chk(self.lib.glp_fri_prove_batch(self.ctx, ctypes.byref(cfg), arr, nb, B, proofs, lens), "glp_fri_prove_batch")
+        out = []
+        for i in range(B):
+            out.append(ctypes.string_at(proofs[i], lens[i]))
+            self.lib.glp_free_host(proofs[i])
+        return out
+
+    @staticmethod
+    def fri_prove_batch_plan(log_n, rate_bits, cap_height, open_masks, arity_bits=4, final_poly_bits=5, num_queries=28, pow_bits=16,
+                             shift=COSET_SHIFT, point_mults=(1,)):
+        """(launches, stream synchronises) one fri_prove_batch call issues for that shape when every PoW search ends in its first
+        window, whatever B is (host only)"""
+        cfg = Prover._fri_config(log_n, rate_bits, cap_height, arity_bits, final_poly_bits, num_queries, pow_bits, shift, point_mults)
+        masks = np.ascontiguousarray(open_masks, dtype=np.uint32)
+        nl, ns = ctypes.c_uint32(), ctypes.c_uint32()
+        rc = load_library().glp_fri_prove_batch_plan(ctypes.byref(cfg), masks.ctypes.data, masks.size, ctypes.byref(nl), ctypes.byref(ns))
+        if rc != 0:
+            raise GlpError(f"glp_fri_prove_batch_plan: {_ERR.get(rc, rc)}")
+        return nl.value, ns.value
+
+    def fri_last_batch_counts(self):
+        """(launches, stream synchronises, PoW windows) of the last fri_prove_batch on this prover"""
+        v = [ctypes.c_uint32() for _ in range(3)]
+        self._chk(self.lib.glp_fri_last_batch_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_fri_last_batch_counts")
+        return tuple(x.value for x in v)
+
+    def pow_grind_batch(self, seeds, pow_bits):
+        """seeds [B][4] -> B nonces, each what pow_grind returns for that seed"""
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(sd.shape[0], dtype=np.uint64)
+        self._chk(self.lib.glp_pow_grind_batch(self.ctx, sd.ctypes.data, sd.shape[0], pow_bits, out.ctypes.data), "glp_pow_grind_batch")
+        return [int(v) for v in out]
+
+    def fri_fold_layer_batch_(self, d_in, in_stride, d_out, out_stride, log_len, arity_bits, shift, betas, B):
+        """one committed fold layer of B codewords on the device (glp_fri_fold_layer_batch); strides in u64 words"""
+        b = np.ascontiguousarray(betas, dtype=np.uint64)
+        self._chk(self.lib.glp_fri_fold_layer_batch(self.ctx, _ptr(d_in), in_stride, _ptr(d_out), out_stride, log_len, arity_bits, shift,
+                                                    b.ctypes.data, B), "glp_fri_fold_layer_batch")
+
+    def fri_fold_layer_batch(self, evals, arity_bits, shift, betas):
+        """evals [B][2^log_len][2] (bit-reversed order over shift*<w>), betas [B][2] -> [B][2^(log_len - arity_bits)][2]: what arity_bits
+        successive fri_fold2 calls give per codeword"""
+        e = np.ascontiguousarray(evals, dtype=np.uint64)
+        B, n = e.shape[0], e.shape[1]
+        log_len = n.bit_length() - 1
+        d = self.to_device(e)
+        o = self.alloc(max(16, B * (16 * n >> arity_bits)))
+        self.fri_fold_layer_batch_(d, 2 * n, o, 2 * n >> arity_bits, log_len, arity_bits, shift, betas, B)
+        out = o.download((B, n >> arity_bits, 2))
+        d.free()
+        o.free()
+        return out
 
     def _verify(self, what, call, proof):
         """True = accepted, False = rejected (reason in self.last_reject); bad arguments raise"""

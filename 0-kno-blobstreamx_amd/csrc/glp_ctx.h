@@ -53,6 +53,8 @@ struct glp_ctx {
     std::vector<std::pair<std::string, float>> stages;
     std::chrono::steady_clock::time_point stage_t0;
     std::string stage_name;
+    // what the last glp_fri_prove_batch issued: kernel launches, stream synchronises, PoW windows searched (glp_fri_last_batch_counts)
+    uint32_t fri_batch_counts[3] = {0, 0, 0};
 };
 
 // stage timing tree of the prover drivers (the TimingTree of the upstream prover, recalled): a

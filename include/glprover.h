@@ -202,6 +202,38 @@ int glp_fri_prove(glp_ctx* ctx, const glp_fri_config* cfg, const glp_fri_batch* 
                   uint8_t** proof, size_t* proof_len);
 void glp_free_host(void* p);
 
+/* B opening proofs of ONE shape. batches: [B][n_batches], instance-major. For every batch index, n_polys and open_mask must be equal in
+ * all instances; device pointers and caps are per instance (an instance may share a batch — e.g. a preprocessed commitment — with
+ * others by pointing at the same memory). proofs[i] / proof_lens[i]: as glp_fri_prove gives for instance i alone, BYTE FOR BYTE.
+ * All or nothing: on any error every proofs[i] is NULL, nothing is leaked, glp_last_error names the instance where one is at fault.
+ * B == 0 is GLP_OK and does nothing.
+ * The B transcripts advance in lock-step on the host; every device step is shared by the whole batch.  Whatever B is, one call issues
+ *   launches     = 3 (z^j tables, openings, combine) + sum over the L fold layers of (glp_merkle_batch_plan launches of the layer's
+ *                  tree of 2^(log_len - arity_bits) leaves, default fusion, + 1 fold launch) + (pow_bits ? 1 : 0) + 1 (the gather)
+ *   synchronises = 1 (openings) + L (layer caps) + 1 (final codewords) + (pow_bits ? 1 : 0) + 1 (the gather)
+ * with L = (log_n - final_poly_bits) / arity_bits (0 when log_n <= final_poly_bits), plus one launch and one synchronise for every
+ * PoW window after the first.  glp_fri_prove's limits apply; GLP_E_INVALID also for shapes that differ between instances, a launch
+ * of more than 2^31 - 1 workgroups and a footprint that overflows.  All temporaries come from the ctx pool and are held until the
+ * call returns.  LDE rows are read 16 bytes at a time when every d_lde is 16-byte aligned (8-byte reads otherwise).
+ * Measured (profiles/fri_batch.json; the 2^16 x 144 leaf's opening proof, medians of 20 alternating repeats, ms): B sequential glp_fri_prove calls
+ * against one call here — B = 1: 2.860 / 2.316, B = 2: 5.711 / 3.284, B = 4: 11.461 / 5.525, B = 8: 23.083 / 10.843, B = 16: 45.965 / 20.489; every B
+ * gains by more than the baseline's own spread (max - min 0.04 - 0.40 ms), B = 1 included (-19 %). */
+int glp_fri_prove_batch(glp_ctx* ctx, const glp_fri_config* cfg, const glp_fri_batch* batches, uint32_t n_batches, uint32_t B,
+                        uint8_t** proofs, size_t* proof_lens);
+/* what one glp_fri_prove_batch call issues for that shape when every PoW search ends in its first window; host only, no ctx */
+int glp_fri_prove_batch_plan(const glp_fri_config* cfg, const uint32_t* open_masks, uint32_t n_batches,
+                             uint32_t* n_launches, uint32_t* n_host_syncs);
+/* counts of the LAST glp_fri_prove_batch on this ctx (kernel launches, stream synchronises, PoW windows searched) */
+int glp_fri_last_batch_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs, uint32_t* pow_windows);
+/* B seeds [B][4] -> B nonces, each exactly what glp_pow_grind returns for that seed (same window rule: the smallest accepted nonce
+ * of the first window that has one) */
+int glp_pow_grind_batch(glp_ctx* ctx, const uint64_t* h_seeds, uint32_t B, uint32_t pow_bits, uint64_t* h_nonces);
+/* one committed fold layer for B codewords: instance b reads d_in + b*in_stride ([2^log_len][2] words), writes d_out + b*out_stride
+ * ([2^(log_len-arity_bits)][2]); equals arity_bits successive glp_fri_fold2 calls with beta, beta^2, beta^4.. and shift, shift^2..
+ * d_in and d_out are 16-byte aligned and both strides even (16-byte accesses); arity_bits 1..5 <= log_len <= 32. */
+int glp_fri_fold_layer_batch(glp_ctx* ctx, const uint64_t* d_in, uint64_t in_stride, uint64_t* d_out, uint64_t out_stride, uint32_t log_len,
+                             uint32_t arity_bits, uint64_t shift, const uint64_t* h_betas /*[B][2]*/, uint32_t B);
+
 /* ---- prover for the build-defined circuit (rows a6, a7 + driver; upstream names recalled:
  *      plonk::prover::prove, compute_partial_products_and_z_polys, compute_quotient_polys, gates::{arithmetic_base,
  *      constant, public_input, poseidon}).
