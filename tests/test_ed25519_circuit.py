@@ -1,7 +1,8 @@
 """Ed25519 verification in-circuit (0-kno-blobstreamx_amd/ed25519_circuit.py): the non-native field arithmetic against Python integers, the
 witness evaluator's product op against the builder, SHA-512 by bit decomposition against hashlib, the curve formulas against a textbook affine
 implementation, and the whole statement on the RFC 8032 §7.1 vectors and the OpenSSL-made fixtures (tests/golden/ed25519.json): valid signatures can
-be laid down, invalid ones cannot; a recorded circuit replays other signatures through the C evaluator and refuses forged ones.  GPU: one signature
+be laid down, invalid ones cannot; a recorded circuit replays other signatures through the C evaluator and refuses forged ones; keys and R with
+small-order components get the oracle's verdict, and hand-built malicious witnesses meet the canonicity constraints.  GPU: one signature
 proved and verified by both verifiers."""
 import hashlib
 import importlib
@@ -204,6 +205,137 @@ def test_recorded_circuit_replays_other_signatures_and_refuses_forgeries():
         prog.evaluate(consts, ec.witness_inputs(pub2, sig2, msg1), threads=1)
     with pytest.raises(ValueError):                                          # ... or under another key
         prog.evaluate(consts, ec.witness_inputs(pub1, sig2, msg2), threads=1)
+
+
+# ---- adversarial inputs (tests/ed25519_cases.py): small-order components, and the constraints a malicious prover faces ---------------------------
+def _accepts(ec, pub, sig, msg):
+    try:
+        ec.ed25519_circuit(object(), pub, sig, msg)
+        return True
+    except ValueError:
+        return False
+
+
+def test_torsion_verdicts_match_the_oracle():
+    """half_size_pair's claim — the split form [u S]B = [u]R + [+-v]A is EXACTLY the cofactorless equation, also for keys and R with small-order
+    components: the circuit accepts exactly what the Python-integer oracle accepts, on mixed-order keys (valid, and valid only under the
+    cofactored equation), pure-torsion keys, the identity as the key, and S = L"""
+    import ed25519_cases as edc
+    ec, _ = _mods()
+    edo = edc.edo
+    mixed = edc.mixed_order()
+    picked = [t for t, kind in mixed if kind][:2] + [t for t, kind in mixed if not kind][:2]
+    # a key of order 8 whose three R = [S]B + [j]T8 give one valid and two invalid signatures
+    group = next(g for i, _, g in edc.torsion_groups() if i % 2 and sum(edo.verify(pub, msg, sig) for pub, sig, msg in g) == 1)
+    picked += group
+    ident = edc.encode(edc.IDENTITY)
+    picked.append((ident, ident + (0).to_bytes(32, "little"), b"the identity signs everything"))           # [0]B = O + [k]O
+    picked.append((ident, ident + edc.L.to_bytes(32, "little"), b"the identity signs everything"))         # [L]B = O too, but S = L is not canonical
+    want = [edo.verify(pub, msg, sig) for pub, sig, msg in picked]
+    assert len(picked) == 9 and want == [True, True, False, False] + [edo.verify(pub, msg, sig) for pub, sig, msg in group] + [True, False]
+    for (pub, sig, msg), w in zip(picked, want):
+        assert _accepts(ec, pub, sig, msg) == w, (pub.hex(), sig.hex(), msg)
+
+
+def _half_pair(kk, ell):
+    """the lattice reduction of ed25519_circuit.half_size_pair restated, started from (1, kk) WITHOUT reducing kk mod L first: (u, v, neg) with
+    u odd and u kk = +-v (mod 8L)"""
+    b1, b2 = (1, kk), (0, 8 * ell)
+    norm = lambda v: v[0] * v[0] + v[1] * v[1]
+    if norm(b1) > norm(b2):
+        b1, b2 = b2, b1
+    while True:
+        mu = (b1[0] * b2[0] + b1[1] * b2[1] + norm(b1) // 2) // norm(b1)
+        b2 = (b2[0] - mu * b1[0], b2[1] - mu * b1[1])
+        if norm(b2) >= norm(b1):
+            break
+        b1, b2 = b2, b1
+    cands = [c for c in (b1, b2, (b1[0] + b2[0], b1[1] + b2[1]), (b1[0] - b2[0], b1[1] - b2[1])) if c[0] & 1]
+    t, r = min(cands, key=lambda c: max(abs(c[0]), abs(c[1])))
+    if r < 0:
+        t, r = -t, -r
+    assert (abs(t) * kk - (-r if t < 0 else r)) % (8 * ell) == 0
+    return abs(t), r, t < 0
+
+
+def _hand_vector(pub, R, S, msg, xa, xr, k_shift=0, double_uv=False):
+    """the input vector of verify_statement(flag=None, split_scalars=True), from Python integers and hashlib only: A, R, S, message bytes; the limbs
+    of x_A, x_R, t, k (11 each); u, v (6 each), neg; q1 (7), w (11), q2 (7).  S is an integer (it may exceed L).  k_shift: k + k_shift * L with
+    t - k_shift, and the half-size pair of THAT k.  double_uv: (2u, 2v).  Every integer relation of the statement holds either way:
+    h = t L + k, u S = q1 L + w, u k -+ v = q2 8L"""
+    import ed25519_cases as edc
+    ell = edc.L
+    lim = lambda v, n=11: [(v >> (24 * i)) & 0xFFFFFF for i in range(n)]
+    h = int.from_bytes(hashlib.sha512(R + pub + msg).digest(), "little")
+    t, k = divmod(h, ell)
+    t, k = t - k_shift, k + k_shift * ell
+    u, v, neg = _half_pair(k, ell)
+    if double_uv:
+        u, v = 2 * u, 2 * v
+    assert u < 1 << 144 and v < 1 << 144
+    q1, w = divmod(u * S, ell)
+    q2, rem = divmod(u * k - (-v if neg else v), 8 * ell)
+    assert rem == 0 and q2 >= 0 and h == t * ell + k
+    return (list(pub) + list(R) + list(S.to_bytes(32, "little")) + list(msg) + lim(xa) + lim(xr) + lim(t) + lim(k) + lim(u, 6) + lim(v, 6)
+            + [1 if neg else 0] + lim(q1, 7) + lim(w) + lim(q2, 7))
+
+
+MALICIOUS_MSG = b"a malicious prover builds its own witness"
+
+
+def _malicious_vectors():
+    """((honest vector, pub, sig), {name: (vector, pub, sig)}) for the message MALICIOUS_MSG"""
+    import ed25519_cases as edc
+    p, ell, msg = edc.p, edc.L, MALICIOUS_MSG
+    seed = hashlib.sha256(b"malicious witnesses, seed 0").digest()       # seed 0: a half-size pair below 2^144 exists for k and for k + L
+    pub, sig = edc.sign(seed, msg)
+    a, _ = edc.secret_of(seed)
+    R, S = sig[:32], int.from_bytes(sig[32:], "little")
+    xa, xr = edc.edo.decode_point(pub)[0], edc.edo.decode_point(R)[0]
+    ident_noncanonical = (p + 1).to_bytes(32, "little")                    # y = p + 1 = 1 (mod p): the identity, if y < p were not enforced
+    ident_signed = ((1 << 255) | 1).to_bytes(32, "little")                 # y = 1 with the sign bit: x = 0 has parity 0
+    SB = edc.mul(S, edc.B)
+    RB = edc.encode(SB)                                                     # [S]B = RB + [k]O for the identity key O, whatever k is
+    cases = {
+        "(2u, 2v)": (_hand_vector(pub, R, S, msg, xa, xr, double_uv=True), pub, sig),                       # only `u odd` refuses it
+        "S + L": (_hand_vector(pub, R, S + ell, msg, xa, xr), pub, R + (S + ell).to_bytes(32, "little")),
+        "k + L with t - 1": (_hand_vector(pub, R, S, msg, xa, xr, k_shift=1), pub, sig),
+        "A: y = p + 1, x = 0": (_hand_vector(ident_noncanonical, RB, S, msg, 0, SB[0]), ident_noncanonical, RB + sig[32:]),
+        "A: y = 1 with the sign bit, x = 0": (_hand_vector(ident_signed, RB, S, msg, 0, SB[0]), ident_signed, RB + sig[32:]),
+        "A: y = 1 with the sign bit, x = p": (_hand_vector(ident_signed, RB, S, msg, p, SB[0]), ident_signed, RB + sig[32:]),
+    }
+    # the same three encodings as R: [S]B = O + [k]A needs S = k a
+    for name, enc, x in (("R: y = p + 1, x = 0", ident_noncanonical, 0), ("R: y = 1 with the sign bit, x = 0", ident_signed, 0),
+                         ("R: y = 1 with the sign bit, x = p", ident_signed, p)):
+        S2 = edc.hash_k(enc, pub, msg) * a % ell
+        assert edc.mul(S2, edc.B) == edc.mul(edc.hash_k(enc, pub, msg), edc.edo.decode_point(pub))           # [S]B = O + [k]A does hold
+        cases[name] = (_hand_vector(pub, enc, S2, msg, xa, x), pub, enc + S2.to_bytes(32, "little"))
+    return (_hand_vector(pub, R, S, msg, xa, xr), pub, sig), cases
+
+
+def _lay_down(ec, monkeypatch, vector, pub, sig):
+    """the circuit of the statement on a given input vector: witness_inputs is replaced by a function that returns it"""
+    monkeypatch.setattr(ec, "witness_inputs", lambda *a, **kw: list(vector))
+    try:
+        return ec.ed25519_circuit(object(), pub, sig, MALICIOUS_MSG)
+    finally:
+        monkeypatch.undo()
+
+
+def test_constraints_reject_malicious_witnesses(monkeypatch):
+    """witness_inputs refuses a non-canonical encoding before a single constraint is evaluated; a malicious prover does not call it.  Here the
+    statement is laid down on HAND-BUILT input vectors in which every integer relation holds and the claimed curve equation is true of the
+    points, so that one canonicity constraint alone stands in the way: u odd, S <= L - 1, k <= L - 1, y <= p - 1, x <= p - 1, the parity of x"""
+    ec, _ = _mods()
+    (honest, pub, sig), cases = _malicious_vectors()
+    assert honest == ec.witness_inputs(pub, sig, MALICIOUS_MSG)
+    _lay_down(ec, monkeypatch, honest, pub, sig)                            # the hand-built honest vector is accepted
+    assert len(cases) == 9
+    for name, (vector, pub_, sig_) in cases.items():
+        assert len(vector) == len(honest), name
+        with pytest.raises(ValueError):
+            _lay_down(ec, monkeypatch, vector, pub_, sig_)
+            pytest.fail(f"the circuit accepted the malicious witness: {name}")
 
 
 @pytest.mark.gpu

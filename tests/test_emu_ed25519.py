@@ -71,6 +71,20 @@ def test_emulated_ed25519_witness(emu):
     check_records(cases, out)
 
 
+def test_adversarial_families_every_word(emu):
+    """tests/ed25519_cases.py: valid signatures at every SHA-512 block boundary, random byte strings as encodings, edge and non-canonical y,
+    torsion and mixed-order points, the edges of S — every record equals the oracle's on all 37 words, zero where the oracle has no value"""
+    import ed25519_cases as edc
+    _, k512 = k_tables()
+    for name in "abcde":
+        triples = edc.FAMILIES[name]()
+        pubs, sigs, msgs, lens, stride = edc.marshal(triples)
+        out = np.full((len(triples), REC), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        assert emu.emu_ed25519_witness(pubs.ctypes.data, sigs.ctypes.data, msgs.ctypes.data, stride, lens.ctypes.data, len(triples),
+                                       k512.ctypes.data, out.ctypes.data) == 0
+        edc.assert_records(triples, out)
+
+
 def test_invalid_encodings(emu):
     """non-canonical y, a y with no square root, x = 0 with the sign bit set"""
     base = load_cases()[0]

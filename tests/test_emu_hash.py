@@ -171,3 +171,27 @@ def test_emulated_tendermint_merkle_root(emu):
         out = ctypes.create_string_buffer(32)
         assert emu.emu_tm_merkle_root(b"".join(items), leaf_len, n, k256.ctypes.data, out) == 0
         assert out.raw == tm_root(items), (leaf_len, n)
+
+
+# where glp_tm_leaf_kernel's padding turns (the hashed message is 0x00 || leaf): 54 fills one block to the last byte, 55 and 56 are the first
+# two-block lengths, at 62 the 0x80 is the last byte of block 0 and at 63 the first of block 1, 118 is the longest leaf two blocks hold
+TM_LEAF_LENS = [1, 54, 55, 56, 62, 63, 64, 118]
+TM_LEAF_COUNTS = [1, 2, 3, 257]                        # a single leaf, a pair, an odd promotion, more than one block of 256 work-items
+
+
+def tm_leaves(leaf_len, n):
+    rng = np.random.default_rng(1000 * leaf_len + n)
+    return [rng.integers(0, 256, leaf_len, dtype=np.uint8).tobytes() for _ in range(n)]
+
+
+@pytest.mark.parametrize("leaf_len", TM_LEAF_LENS)
+def test_emulated_tendermint_fixed_leaves_at_the_padding_branches(emu, leaf_len):
+    """glp_tm_leaf_kernel at every leaf length where its padding takes another branch, for a single leaf, a pair, an odd promotion and more than
+    one block of leaves, vs the recursive RFC 6962 definition on hashlib"""
+    from test_blobstream_host import tm_root
+    k256, _ = k_tables()
+    for n in TM_LEAF_COUNTS:
+        items = tm_leaves(leaf_len, n)
+        out = ctypes.create_string_buffer(32)
+        assert emu.emu_tm_merkle_root(b"".join(items), leaf_len, n, k256.ctypes.data, out) == 0
+        assert out.raw == tm_root(items), (leaf_len, n)

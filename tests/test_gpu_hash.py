@@ -167,3 +167,20 @@ def test_tendermint_merkle_root(prover):
         t = json.load(f)
     for c in t["cases"]:
         assert prover.tm_merkle_root(bytes.fromhex(c["leaves"]), t["leaf_len"]).hex() == c["root"], c["n"]
+
+
+@pytest.mark.parametrize("leaf_len", [1, 54, 55, 56, 62, 63, 64, 118])
+def test_tendermint_fixed_leaves_at_the_padding_branches(prover, leaf_len):
+    """glp_tm_leaf_kernel at every leaf length where its padding takes another branch (the suite ran it at 40 and 64 only), for a single leaf,
+    a pair, an odd promotion and more than one block of leaves, vs the recursive RFC 6962 definition on hashlib"""
+    from test_blobstream_host import tm_root
+    from test_emu_hash import TM_LEAF_COUNTS, tm_leaves
+    for n in TM_LEAF_COUNTS:
+        items = tm_leaves(leaf_len, n)
+        assert prover.tm_merkle_root(b"".join(items), leaf_len) == tm_root(items), (leaf_len, n)
+
+
+def test_tendermint_leaf_longer_than_two_blocks_is_refused(prover, pkg):
+    """119 bytes and the prefix no longer pad into two SHA-256 blocks: GLP_E_INVALID, not a wrong root"""
+    with pytest.raises(pkg.GlpError, match="GLP_E_INVALID"):
+        prover.tm_merkle_root(bytes(119 * 3), 119)
