@@ -203,6 +203,9 @@ def load_library():
         "glp_plonk_setup_ex": (ctypes.c_int, [_vp, ctypes.POINTER(CircuitShape), _vp, _vp, ctypes.POINTER(_vp)]),
         "glp_plonk_prove_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp),
                                               ctypes.POINTER(ctypes.c_size_t)]),
+        "glp_plonk_prove_batch": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t)]),
+        "glp_plonk_last_batch_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "glp_plonk_verify_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_uint32,
                                                ctypes.c_uint32]),
         "glp_plonk_verify_host_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
@@ -839,6 +842,13 @@ class Prover:
         self._chk(self.lib.glp_fri_last_batch_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_fri_last_batch_counts")
         return tuple(x.value for x in v)
 
+    def plonk_last_batch_counts(self):
+        """(launches, stream synchronises) the PLONK driver's own code issued in the last PlonkCircuit.prove_batch_ on this prover; the opening
+        proof's are fri_last_batch_counts()"""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        self._chk(self.lib.glp_plonk_last_batch_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_plonk_last_batch_counts")
+        return tuple(x.value for x in v)
+
     def pow_grind_batch(self, seeds, pow_bits):
         """seeds [B][4] -> B nonces, each what pow_grind returns for that seed"""
         sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, 4)
@@ -1086,6 +1096,44 @@ class PlonkCircuit:
         data = ctypes.string_at(proof.value, ln.value)
         self.prover.lib.glp_free_host(proof)
         return data
+
+    def prove_batch_(self, d_wires_list, publics=None, num_queries=28, pow_bits=16):
+        """B proofs of this circuit in one call (glp_plonk_prove_batch).  d_wires_list: B device wire matrices (DeviceBuffers or addresses; read
+        only, the same one may appear twice); publics: B lists of public values (None when the circuit has none).  Returns the B proofs, each
+        byte for byte what prove_ returns for that instance alone; any error fails the whole call (GlpError names the instance at fault)."""
+        B = len(d_wires_list)
+        if B == 0:
+            return []
+        if publics is None:
+            publics = [None] * B
+        if len(publics) != B:
+            raise GlpError(f"{len(publics)} public-input lists given for {B} instances")
+        rows = [self._public_words(p) for p in publics]
+        pub = np.ascontiguousarray(np.stack(rows), dtype=np.uint64) if self.n_public else None
+        ptrs = (_vp * B)(*[_ptr(d) for d in d_wires_list])
+        proofs = (_vp * B)()
+        lens = (ctypes.c_size_t * B)()
+        self.prover._chk(self.prover.lib.glp_plonk_prove_batch(self.prover.ctx, self.h, ptrs, pub.ctypes.data if pub is not None else None, B,
+                                                               num_queries, pow_bits, proofs, lens), "glp_plonk_prove_batch")
+        out = []
+        for i in range(B):
+            out.append(ctypes.string_at(proofs[i], lens[i]))
+            self.prover.lib.glp_free_host(proofs[i])
+        return out
+
+    def prove_batch(self, wires_list, publics=None, num_queries=28, pow_bits=16):
+        """prove_batch_ for host arrays: B wire matrices [n_wires][n]"""
+        n = 1 << self.log_n
+        bufs = []
+        try:
+            for w in wires_list:
+                w = np.ascontiguousarray(w, dtype=np.uint64)
+                assert w.shape == (self.n_wires, n)
+                bufs.append(self.prover.to_device(w))
+            return self.prove_batch_(bufs, publics, num_queries, pow_bits)
+        finally:
+            for b in bufs:
+                b.free()
 
     def debug_stage(self, wires, which, challenges, public=None):
         """parity hook (glp_plonk_debug_stage): which = "zs" -> [2*M][n] Z / partial products on the trace domain for

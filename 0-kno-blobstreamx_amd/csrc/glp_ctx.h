@@ -55,6 +55,8 @@ struct glp_ctx {
     std::string stage_name;
     // what the last glp_fri_prove_batch issued: kernel launches, stream synchronises, PoW windows searched (glp_fri_last_batch_counts)
     uint32_t fri_batch_counts[3] = {0, 0, 0};
+    // what the PLONK driver's own code issued in the last glp_plonk_prove_batch: kernel launches, stream synchronises (glp_plonk_last_batch_counts)
+    uint32_t plonk_batch_counts[2] = {0, 0};
 };
 
 // stage timing tree of the prover drivers (the TimingTree of the upstream prover, recalled): a

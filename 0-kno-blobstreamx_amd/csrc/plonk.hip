@@ -17,10 +17,13 @@
 #include "hash_state.h"
 #include "challenger.h"
 #include "plonk_kernels.cuh"
+#include "plonk_batch_kernels.cuh"
 
 int glp_ntt_table(glp_ctx* c, int log_N, int inv, const u64** lo, const u64** hi);
 int glp_fri_prove_impl(glp_ctx* c, const glp_fri_config* cfg, const glp_fri_batch* batches, uint32_t n_batches, glp_challenger& ch,
                        std::vector<u64>& P);
+int glp_fri_prove_batch_impl(glp_ctx* c, const glp_fri_config* cfg, const glp_fri_batch* batches, uint32_t n_batches, uint32_t B,
+                             glp_challenger* chs[], std::vector<u64> Ps[]);
 uint8_t* glp_words_to_blob(const std::vector<u64>& P, size_t* len);
 
 namespace {
@@ -457,4 +460,305 @@ extern "C" int glp_plonk_prove_ex(glp_ctx* c, glp_plonk_circuit* ck, const uint6
     glp_stage_mark(c, nullptr);
     *proof_out = glp_words_to_blob(P, proof_len);
     return *proof_out ? GLP_OK : GLP_E_NOMEM;
+}
+
+// ---- B proofs of one circuit per call (kernels: plonk_batch_kernels.cuh) ----------------------------------------------------------
+namespace {
+static_assert(sizeof(GlpPlonkInst) % 8 == 0, "the descriptor table is staged in a vector of words");
+constexpr size_t INST_WORDS = sizeof(GlpPlonkInst) / 8;
+// host memory that asynchronous copies of one call read: it lives in the entry point's frame, which does not return before the stream has
+// taken it (the last synchronise of a successful call comes after every copy; a failed call synchronises before it returns)
+struct BatchHost {
+    std::vector<u64> desc;       // [B] GlpPlonkInst, then the alpha powers [B][NCHAL][n_con]
+    std::vector<u64> scale;      // shift^-j: lo[4096], then hi[N >> 12]
+};
+constexpr u32 PLONK_BATCH_MAX_BLOCKS = 0x7fffffffu;
+// every temporary comes from the ctx pool (glp_pool_alloc has set the error text)
+#define POOL_ALLOC(buf, bytes) do { if ((buf).alloc(bytes) != hipSuccess) return GLP_E_NOMEM; } while (0)
+
+int prove_batch_impl(glp_ctx* c, glp_plonk_circuit* ck, const uint64_t* const* d_wire_vals, const uint64_t* h_public, u32 B, u32 num_queries,
+                     u32 pow_bits, BatchHost& H, std::vector<glp_challenger>& chs, std::vector<std::vector<u64>>& Ps, u32* counts) {
+    const u32 log_n = ck->log_n, W = ck->W, rb = ck->rate_bits, M = ck->R / GLP_PLONK_CHUNK, NP = ck->n_public;
+    const u32 log_N = log_n + rb, NZ = GLP_PLONK_NCHAL * M, NQ = GLP_PLONK_NCHAL << rb;
+    const u64 n = 1ull << log_n, N = 1ull << log_N;
+    const u32 chh = ck->cap_h < log_N ? ck->cap_h : log_N;
+    const u64 dig_words = 4 * ((2ull << log_N) - (1ull << chh));
+    const size_t cap_words = (size_t)4 << chh;
+    const u32 n_con = n_constraints(ck);
+    const u32 bpi_n = (u32)((n + 255) / 256), bpi_N = (u32)((N + 255) / 256);
+    int rc;
+
+    // the statement first, every instance: exactly what glp_plonk_prove_ex binds before the first challenge
+    for (u32 i = 0; i < B; i++) {
+        std::vector<u64>& P = Ps[i];
+        glp_challenger& ch = chs[i];
+        auto put = [&](u64 v) { P.push_back(v); ch.observe(v % GL_P); };
+        put(0x32304B4C504C4747ull /* "GGLPLK02" */); put(log_n); put(W); put(ck->R); put(rb); put(ck->cap_h); put(NP); put(ck->flags);
+        for (u32 k = 0; k < NP; k++) put(h_public[(size_t)i * NP + k]);
+        for (u64 v : ck->pre.cap) put(v);
+    }
+    auto observe_caps = [&](const std::vector<u64>& caps) {
+        for (u32 i = 0; i < B; i++)
+            for (size_t k = 0; k < cap_words; k++) { const u64 v = caps[(size_t)i * cap_words + k]; Ps[i].push_back(v); chs[i].observe(v % GL_P); }
+    };
+    std::vector<u64> caps((size_t)B * cap_words);
+
+    // the descriptor table [B] and, behind it, the alpha powers; uploaded once per stage that reads new fields
+    H.desc.assign((size_t)B * INST_WORDS + (size_t)B * GLP_PLONK_NCHAL * n_con, 0);
+    GlpPlonkInst* inst = reinterpret_cast<GlpPlonkInst*>(H.desc.data());
+    DBuf d_desc(c);
+    POOL_ALLOC(d_desc, H.desc.size() * 8);
+    const GlpPlonkInst* d_inst = reinterpret_cast<const GlpPlonkInst*>(d_desc.p);
+    const u64* d_apow = d_desc.u() + (size_t)B * INST_WORDS;
+    auto upload_insts = [&](bool with_alpha) {
+        return hipMemcpyAsync(d_desc.p, H.desc.data(), (with_alpha ? H.desc.size() : (size_t)B * INST_WORDS) * 8, hipMemcpyHostToDevice, c->stream);
+    };
+
+    c->stages.clear(); c->stage_name.clear();
+    glp_stage_mark(c, "commit_wires(ifft+lde+merkle)");
+    // ---- wires: the B matrices side by side, one commitment call -----------------------------------
+    DBuf w_co(c), w_lde(c), w_dig(c);
+    POOL_ALLOC(w_co, (size_t)B * W * n * 8);
+    POOL_ALLOC(w_lde, (size_t)B * W * N * 8);
+    POOL_ALLOC(w_dig, (size_t)B * dig_words * 8);
+    for (u32 i = 0; i < B; i++) inst[i].wire_vals = d_wire_vals[i];
+    GLP_HIPCHK(c, upload_insts(false));
+    {
+        const u64 words = (u64)W * n;
+        const u64 want = (words + 255) / 256;
+        const u32 bpi = (u32)(want < 2048 ? want : 2048);
+        hipLaunchKernelGGL(glp_plonk_gather_wires_batch_kernel<0>, dim3(bpi * B), dim3(256), 0, c->stream, d_inst, words, bpi, w_co.u());
+        GLP_HIPCHK(c, hipGetLastError());
+        counts[0]++;
+    }
+    rc = glp_commit_values_batch(c, w_co.u(), W, log_n, rb, chh, B, w_lde.u(), w_dig.u(), dig_words, caps.data());
+    if (rc) return rc;
+    observe_caps(caps);
+    std::vector<u64> w_caps = caps;                      // the FRI batches point at the caps until the call returns
+    for (u32 i = 0; i < B; i++) {
+        for (int t = 0; t < GLP_PLONK_NCHAL; t++) inst[i].beta[t] = chs[i].challenge();
+        for (int t = 0; t < GLP_PLONK_NCHAL; t++) inst[i].gamma[t] = chs[i].challenge();
+    }
+
+    glp_stage_mark(c, "perm_products(K6)");
+    // ---- K6: Z and partial products, [B*NCHAL*M][n] ---------------------------------------------------
+    DBuf z_co(c), z_lde(c), z_dig(c);
+    POOL_ALLOC(z_co, (size_t)B * NZ * n * 8);
+    {
+        const u64* wn_lo = nullptr; const u64* wn_hi = nullptr;
+        rc = glp_ntt_table(c, (int)log_n, 0, &wn_lo, &wn_hi);
+        if (rc) return rc;
+        const u32 nb = (u32)((n + GLP_SCAN_BLOCK - 1) / GLP_SCAN_BLOCK);
+        DBuf qv(c), rr(c), bprod(c);
+        POOL_ALLOC(qv, (size_t)B * NZ * n * 8);
+        POOL_ALLOC(rr, (size_t)B * GLP_PLONK_NCHAL * n * 8);
+        POOL_ALLOC(bprod, (size_t)B * GLP_PLONK_NCHAL * nb * 8);
+        for (u32 i = 0; i < B; i++) { inst[i].qv = qv.u() + (size_t)i * NZ * n; inst[i].rr = rr.u() + (size_t)i * GLP_PLONK_NCHAL * n; }
+        GLP_HIPCHK(c, upload_insts(false));
+        GlpPermArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.sigmas = ck->sigma_vals.u(); pa.ks = ck->ks.u(); pa.log_n = log_n; pa.W = ck->R; pa.w_lo = wn_lo; pa.w_hi = wn_hi;
+        hipLaunchKernelGGL(glp_perm_quotients_batch_kernel<0>, dim3(bpi_n * B), dim3(256), 0, c->stream, pa, d_inst, bpi_n);
+        GLP_HIPCHK(c, hipGetLastError());
+        // the scan kernels index by challenge: over [B*NCHAL]-major buffers, B*NCHAL challenges are the batch
+        const u32 rows = B * GLP_PLONK_NCHAL;
+        hipLaunchKernelGGL(glp_scan_reduce_kernel<0>, dim3(nb, rows), dim3(256), 0, c->stream, rr.u(), n, bprod.u());
+        GLP_HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(glp_scan_blocks_kernel<0>, dim3(rows), dim3(GLP_SCAN_TOP), 0, c->stream, bprod.u(), nb);
+        GLP_HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(glp_scan_apply_kernel<0>, dim3(nb, rows), dim3(256), 0, c->stream, rr.u(), qv.u(), n, M, bprod.u(), z_co.u());
+        GLP_HIPCHK(c, hipGetLastError());
+        counts[0] += 4;
+    }
+    glp_stage_mark(c, "commit_zs");
+    POOL_ALLOC(z_lde, (size_t)B * NZ * N * 8);
+    POOL_ALLOC(z_dig, (size_t)B * dig_words * 8);
+    rc = glp_commit_values_batch(c, z_co.u(), NZ, log_n, rb, chh, B, z_lde.u(), z_dig.u(), dig_words, caps.data());
+    if (rc) return rc;
+    observe_caps(caps);
+    std::vector<u64> z_caps = caps;
+
+    glp_stage_mark(c, "quotient(K7)+to_coeffs");
+    // ---- the public-input polynomials and K7 ------------------------------------------------------------
+    DBuf q_co(c), q_lde(c), q_dig(c);
+    POOL_ALLOC(q_co, (size_t)B * GLP_PLONK_NCHAL * N * 8);
+    {
+        DBuf pi_co(c), pi_lde(c), quot_rev(c), d_scale(c);
+        if (NP) {
+            POOL_ALLOC(pi_co, (size_t)B * n * 8);
+            POOL_ALLOC(pi_lde, (size_t)B * N * 8);
+            GLP_HIPCHK(c, hipMemsetAsync(pi_co.p, 0, (size_t)B * n * 8, c->stream));
+            GLP_HIPCHK(c, hipMemcpy2DAsync(pi_co.p, n * 8, h_public, (size_t)NP * 8, (size_t)NP * 8, B, hipMemcpyHostToDevice, c->stream));
+            rc = glp_ntt(c, pi_co.u(), log_n, B, 1);
+            if (rc) return rc;
+            rc = glp_lde_coset(c, pi_co.u(), pi_lde.u(), log_n, rb, B, 7, GLP_NTT_BITREV);
+            if (rc) return rc;
+        }
+        POOL_ALLOC(quot_rev, (size_t)B * GLP_PLONK_NCHAL * N * 8);
+        u64* apow = H.desc.data() + (size_t)B * INST_WORDS;
+        for (u32 i = 0; i < B; i++) {
+            for (int t = 0; t < GLP_PLONK_NCHAL; t++) {
+                const u64 alpha = chs[i].challenge();
+                u64 x = 1;
+                u64* row = apow + ((size_t)i * GLP_PLONK_NCHAL + t) * n_con;
+                for (u32 k = 0; k < n_con; k++) { row[k] = x; x = gl_mul(x, alpha); }
+            }
+            inst[i].wires_lde = w_lde.u() + (size_t)i * W * N;
+            inst[i].zs_lde = z_lde.u() + (size_t)i * NZ * N;
+            inst[i].pi_lde = NP ? pi_lde.u() + (size_t)i * N : nullptr;
+            inst[i].alpha_pow = d_apow + (size_t)i * GLP_PLONK_NCHAL * n_con;
+            inst[i].out = quot_rev.u() + (size_t)i * GLP_PLONK_NCHAL * N;
+        }
+        GLP_HIPCHK(c, upload_insts(true));
+        const u64* wN_lo = nullptr; const u64* wN_hi = nullptr;
+        rc = glp_ntt_table(c, (int)log_N, 0, &wN_lo, &wN_hi);
+        if (rc) return rc;
+        GlpQuotientArgs qa;
+        memset(&qa, 0, sizeof(qa));
+        const u32 n_const = (u32)glp_plonk_n_const(ck->flags);
+        qa.consts = ck->pre.lde.u(); qa.sigmas = ck->pre.lde.u() + (u64)n_const * N;
+        qa.q_ext = (ck->flags & GLP_CIRCUIT_EXT_GATE) ? ck->pre.lde.u() + (u64)(n_const - 1) * N : nullptr;
+        qa.ks = ck->ks.u();
+        qa.log_n = log_n; qa.rate_bits = rb; qa.W = W; qa.R = ck->R; qa.n_con = n_con;
+        qa.pos_consts = c->hash->d_consts; qa.w_lo = wN_lo; qa.w_hi = wN_hi; qa.shift = ck->shift;
+        const u64 sn = gl_pow(ck->shift, n), wr = gl_root_of_unity(rb);
+        for (u32 k = 0; k < (1u << rb); k++) qa.zh_inv[k] = gl_inv(gl_sub(gl_mul(sn, gl_pow(wr, k)), 1));
+        qa.n_inv = gl_inv(n % GL_P);
+        qa.inv_xm1 = ck->inv_xm1.u();
+        const dim3 g(bpi_N * B), blk(256);
+        if ((ck->flags & GLP_CIRCUIT_POSEIDON_GATE) && c->hash->small_mds && !getenv("GLP_K7_GENERIC_MDS"))
+            hipLaunchKernelGGL((glp_quotient_batch_kernel<true, true>), g, blk, 0, c->stream, qa, d_inst, bpi_N);
+        else if (ck->flags & GLP_CIRCUIT_POSEIDON_GATE)
+            hipLaunchKernelGGL(glp_quotient_batch_kernel<true>, g, blk, 0, c->stream, qa, d_inst, bpi_N);
+        else
+            hipLaunchKernelGGL(glp_quotient_batch_kernel<false>, g, blk, 0, c->stream, qa, d_inst, bpi_N);
+        GLP_HIPCHK(c, hipGetLastError());
+        counts[0]++;
+        if (ck->flags & GLP_CIRCUIT_SHA_GATES) {
+            hipLaunchKernelGGL(glp_quotient_sha_batch_kernel<0>, g, blk, 0, c->stream, qa, d_inst, bpi_N, n_con - GLP_SHA_GATE_CONSTRAINTS);
+            GLP_HIPCHK(c, hipGetLastError());
+            counts[0]++;
+        }
+        // evaluations (bit-reversed, coset) -> coefficients: un-bit-reverse, inverse NTT, unshift — B*NCHAL polynomials
+        const u32 rows = B * GLP_PLONK_NCHAL;
+        hipLaunchKernelGGL(glp_bitrev_permute_kernel<0>, dim3((unsigned)(((u64)rows * N + 255) / 256)), blk, 0, c->stream, quot_rev.u(), q_co.u(), log_N, rows);
+        GLP_HIPCHK(c, hipGetLastError());
+        counts[0]++;
+        rc = glp_ntt(c, q_co.u(), log_N, rows, 1);
+        if (rc) return rc;
+        const size_t n_hi = N > 4096 ? (size_t)(N >> 12) : 0;
+        H.scale.resize(4096 + n_hi);
+        {
+            const u64 sinv = gl_inv(ck->shift);
+            u64 t = 1;
+            for (u32 k = 0; k < 4096; k++) { H.scale[k] = t; t = gl_mul(t, sinv); }
+            const u64 s4096 = t;
+            t = 1;
+            for (size_t k = 0; k < n_hi; k++) { H.scale[4096 + k] = t; t = gl_mul(t, s4096); }
+        }
+        POOL_ALLOC(d_scale, H.scale.size() * 8);
+        GLP_HIPCHK(c, hipMemcpyAsync(d_scale.p, H.scale.data(), H.scale.size() * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(glp_scale_pow_kernel<0>, dim3(4096), blk, 0, c->stream, q_co.u(), log_N, rows, d_scale.u(),
+                           n_hi ? d_scale.u() + 4096 : (const u64*)nullptr);
+        GLP_HIPCHK(c, hipGetLastError());
+        counts[0]++;
+    }
+    glp_stage_mark(c, "commit_quotient(lde+merkle)");
+    // [B][NCHAL][8][n] is a dense batch of B * 16 coefficient-form polynomials
+    POOL_ALLOC(q_lde, (size_t)B * NQ * N * 8);
+    POOL_ALLOC(q_dig, (size_t)B * dig_words * 8);
+    rc = glp_lde_coset(c, q_co.u(), q_lde.u(), log_n, rb, B * NQ, 7, GLP_NTT_BITREV);
+    if (rc) return rc;
+    rc = glp_merkle_batch(c, q_lde.u(), (u64)NQ * N, 1, N, NQ, log_N, chh, B, GLP_MERKLE_FUSE_DEFAULT, q_dig.u(), dig_words, caps.data());
+    if (rc) return rc;
+    observe_caps(caps);
+
+    // ---- openings: everything at zeta, the Z batch also at g*zeta ----------------------------------------
+    glp_fri_config fc;
+    memset(&fc, 0, sizeof(fc));
+    fc.log_n = log_n; fc.rate_bits = rb; fc.cap_height = ck->cap_h; fc.arity_bits = 4; fc.final_poly_bits = log_n < 5 ? log_n : 5;
+    fc.num_queries = num_queries; fc.pow_bits = pow_bits; fc.shift = ck->shift;
+    fc.n_points = 2; fc.point_mult[0] = 1; fc.point_mult[1] = gl_root_of_unity(log_n);
+    std::vector<glp_fri_batch> fb((size_t)B * 4);
+    std::vector<glp_challenger*> chp(B);
+    for (u32 i = 0; i < B; i++) {
+        glp_fri_batch* f = &fb[(size_t)i * 4];
+        f[0].d_coeffs = ck->pre.coeffs.u(); f[0].d_lde = ck->pre.lde.u(); f[0].d_digests = ck->pre.dig.u(); f[0].h_cap = ck->pre.cap.data(); f[0].n_polys = ck->pre.n_polys;
+        f[1].d_coeffs = w_co.u() + (size_t)i * W * n; f[1].d_lde = w_lde.u() + (size_t)i * W * N; f[1].d_digests = w_dig.u() + (size_t)i * dig_words;
+        f[1].h_cap = w_caps.data() + (size_t)i * cap_words; f[1].n_polys = W;
+        f[2].d_coeffs = z_co.u() + (size_t)i * NZ * n; f[2].d_lde = z_lde.u() + (size_t)i * NZ * N; f[2].d_digests = z_dig.u() + (size_t)i * dig_words;
+        f[2].h_cap = z_caps.data() + (size_t)i * cap_words; f[2].n_polys = NZ;
+        f[3].d_coeffs = q_co.u() + (size_t)i * NQ * n; f[3].d_lde = q_lde.u() + (size_t)i * NQ * N; f[3].d_digests = q_dig.u() + (size_t)i * dig_words;
+        f[3].h_cap = caps.data() + (size_t)i * cap_words; f[3].n_polys = NQ;
+        for (int b = 0; b < 4; b++) f[b].open_mask = (b == 2) ? 3u : 1u;
+        chp[i] = &chs[i];
+    }
+    return glp_fri_prove_batch_impl(c, &fc, fb.data(), 4, B, chp.data(), Ps.data());
+}
+}  // namespace
+
+extern "C" int glp_plonk_last_batch_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs) {
+    if (!c) return GLP_E_INVALID;
+    if (n_launches) *n_launches = c->plonk_batch_counts[0];
+    if (n_host_syncs) *n_host_syncs = c->plonk_batch_counts[1];
+    return GLP_OK;
+}
+
+extern "C" int glp_plonk_prove_batch(glp_ctx* c, glp_plonk_circuit* ck, const uint64_t* const* d_wire_vals, const uint64_t* h_public, uint32_t B,
+                                     uint32_t num_queries, uint32_t pow_bits, uint8_t** proofs, size_t* proof_lens) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->plonk_batch_counts[0] = c->plonk_batch_counts[1] = 0;
+    if (B == 0) return GLP_OK;
+    if (!ck || !d_wire_vals || !proofs || !proof_lens || num_queries == 0 || num_queries > 256 || pow_bits > 32 || (ck->n_public && !h_public)) {
+        glp_set_err(c, "glp_plonk_prove_batch: bad argument");
+        return GLP_E_INVALID;
+    }
+    for (u32 i = 0; i < B; i++) { proofs[i] = nullptr; proof_lens[i] = 0; }
+    for (u32 i = 0; i < B; i++) {
+        if (!d_wire_vals[i]) { glp_set_err(c, "glp_plonk_prove_batch: instance %u: null wire matrix", i); return GLP_E_INVALID; }
+        for (u32 k = 0; k < ck->n_public; k++)
+            if (h_public[(size_t)i * ck->n_public + k] >= GL_P) {
+                glp_set_err(c, "glp_plonk_prove_batch: instance %u: public input %u not canonical", i, k);
+                return GLP_E_INVALID;
+            }
+    }
+    if (!c->hash || !c->hash->have_consts) { glp_set_err(c, "Poseidon constants not set"); return GLP_E_STATE; }
+    {
+        // every launch is 1-D over the batch: B * N / 256 workgroups for K7, twice that for the un-bit-reversal; rows of the NTT calls are 32-bit
+        const u64 N = 1ull << (ck->log_n + ck->rate_bits);
+        const u64 most_blocks = ((u64)B * GLP_PLONK_NCHAL * N + 255) / 256;
+        const u32 widest = ck->W > (GLP_PLONK_NCHAL << ck->rate_bits) ? ck->W : (GLP_PLONK_NCHAL << ck->rate_bits);
+        if (most_blocks > PLONK_BATCH_MAX_BLOCKS || (u64)B * widest > 0xffffffffull || (u64)B * GLP_PLONK_NCHAL > 65535) {
+            glp_set_err(c, "glp_plonk_prove_batch: B = %u is more than one call takes at this size (a launch of more than 2^31 - 1 workgroups)", B);
+            return GLP_E_UNSUPPORTED;
+        }
+    }
+    BatchHost H;
+    std::vector<glp_challenger> chs(B);
+    for (glp_challenger& ch : chs) {
+        memset(ch.state, 0, sizeof(ch.state));
+        ch.n_in = ch.n_out = 0;
+        ch.consts = c->hash->h_consts;
+        ch.small_mds = c->hash->small_mds;
+    }
+    std::vector<std::vector<u64>> Ps(B);
+    u32 counts[2] = {0, 0};
+    int rc = prove_batch_impl(c, ck, d_wire_vals, h_public, B, num_queries, pow_bits, H, chs, Ps, counts);
+    c->plonk_batch_counts[0] = counts[0]; c->plonk_batch_counts[1] = counts[1];
+    if (rc) {
+        hipStreamSynchronize(c->stream);        // copies still in flight read H and the caller's h_public (not counted: not on the path of a proof)
+        return rc;
+    }
+    glp_stage_mark(c, nullptr);
+    for (u32 i = 0; i < B; i++) {
+        proofs[i] = glp_words_to_blob(Ps[i], &proof_lens[i]);
+        if (!proofs[i]) {
+            for (u32 k = 0; k < i; k++) { free(proofs[k]); proofs[k] = nullptr; }
+            for (u32 k = 0; k < B; k++) proof_lens[k] = 0;
+            glp_set_err(c, "glp_plonk_prove_batch: out of host memory at instance %u", i);
+            return GLP_E_NOMEM;
+        }
+    }
+    return GLP_OK;
 }

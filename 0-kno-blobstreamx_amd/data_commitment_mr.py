@@ -18,7 +18,7 @@ import time
 
 import numpy as np
 
-from . import SHA_GATE_WIRES, poseidon_permute_host
+from . import SHA_GATE_WIRES, DeviceBuffer, poseidon_permute_host
 from .gadgets import Sha256Rows
 from .recursion import CircuitBuilder
 
@@ -89,13 +89,16 @@ class DataCommitmentMapReduce:
         return 80
 
     def __init__(self, prover, poseidon_consts, leaf_blocks=64, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
-                 device_witness_chunk=32):
+                 device_witness_chunk=32, prove_batch=0):
         """map_provers: further Provers on the same GPU (their Poseidon constants set): the Map step then proves leaves on all of them at once,
         one host thread each (the latency-bound phases of one leaf proof overlap the throughput-bound phases of another, as in mapreduce.py).
         device_witness (default off: the host evaluator pool): the Map step evaluates the leaves' witness programs ON THE DEVICE, device_witness_chunk
         leaves per launch (WitnessProgram.evaluate_device; 32 signature leaves are a 340 MB slab), and the provers place and prove from the slab.
         The Reduce step does the same with the nodes of a level (RecursionProgram.witness_batch: the segmented plan and the word checks on the
-        device), so that no host evaluator runs anywhere."""
+        device), so that no host evaluator runs anywhere.
+        prove_batch (default 0: one prover call per leaf): with k > 0 every prover of the Map step places contiguous groups of up to k leaves of
+        its share side by side in a [k][W][n] buffer of its own (allocated once) and proves each group with ONE PlonkCircuit.prove_batch_ call:
+        the same proofs, byte for byte.  The Reduce levels are not batched."""
         assert leaf_blocks >= 1 and leaf_blocks & (leaf_blocks - 1) == 0 and fan_in >= 2 and fan_in & (fan_in - 1) == 0
         self.prover, self.consts = prover, tuple(np.ascontiguousarray(a, dtype=np.uint64) for a in poseidon_consts)
         self.map_provers, self.map_circuits = list(map_provers), []
@@ -105,6 +108,18 @@ class DataCommitmentMapReduce:
         self.node_replicas = {}         # id(node program) -> [its replicas on each map prover]
         self.record_seconds = {}
         self.device_witness, self.device_witness_chunk = bool(device_witness), max(1, int(device_witness_chunk))
+        self.prove_batch, self._batch_bufs = max(0, int(prove_batch)), {}
+
+    def _prove_group(self, prover, circuit, place, count):
+        """one prove_batch_ call for `count` <= prove_batch leaves: place(j, address) lays leaf j's wire matrix at that address of this prover's
+        [k][W][n] buffer and returns its public values; returns the proofs in order"""
+        words = self.leaf_program.W << self.leaf_program.log_n
+        buf = self._batch_bufs.get(id(prover))
+        if buf is None or buf.ptr is None or buf.prover is not prover:
+            buf = self._batch_bufs[id(prover)] = DeviceBuffer(prover, self.prove_batch * words * 8)
+        addrs = [buf.ptr + j * words * 8 for j in range(count)]
+        publics = [place(j, addrs[j]) for j in range(count)]
+        return circuit.prove_batch_(addrs, publics, self.nq, self.pw)
 
     # ---- Map ----------------------------------------------------------------------------------------------------------------------
     def _record_leaf(self):
@@ -157,7 +172,14 @@ class DataCommitmentMapReduce:
                     self.map_provers[w - 1].bind_thread()
                 prover, circuit = (self.prover, self.leaf_circuit) if w == 0 else (self.map_provers[w - 1], self.map_circuits[w - 1])
                 out = []
-                for i in range(w, len(inputs_list), n_workers):
+                share = range(w, len(inputs_list), n_workers)
+                if self.prove_batch:
+                    for g in range(0, len(share), self.prove_batch):
+                        ids = share[g:g + self.prove_batch]
+                        place = lambda j, addr, ids=ids: self.leaf_program.device_witness(prover, futs[ids[j]].result(), out=addr)[1]
+                        out += zip(ids, self._prove_group(prover, circuit, place, len(ids)))
+                    return out
+                for i in share:
                     dw, public = self.leaf_program.device_witness(prover, futs[i].result(), reuse=True)
                     out.append((i, circuit.prove_(dw, self.nq, self.pw, public=public)))
                 return out
@@ -198,7 +220,15 @@ class DataCommitmentMapReduce:
                     if w:
                         self.map_provers[w - 1].bind_thread()
                     prover, circuit = (self.prover, self.leaf_circuit) if w == 0 else (self.map_provers[w - 1], self.map_circuits[w - 1])
-                    for i in range(w, len(part), n_workers):
+                    share = range(w, len(part), n_workers)
+                    if self.prove_batch:
+                        for g in range(0, len(share), self.prove_batch):
+                            ids = share[g:g + self.prove_batch]
+                            place = lambda j, addr, ids=ids: slab.device_witness(prover, ids[j], out=addr)[1]
+                            for i, proof in zip(ids, self._prove_group(prover, circuit, place, len(ids))):
+                                out[lo + i] = proof
+                        return
+                    for i in share:
                         dw, public = slab.device_witness(prover, i, reuse=True)
                         out[lo + i] = circuit.prove_(dw, self.nq, self.pw, public=public)
                 if pool is None:
@@ -407,6 +437,10 @@ class DataCommitmentMapReduce:
         for rp in self.nodes.values():
             rp.free()
         self.nodes = {}
+        for buf in self._batch_bufs.values():
+            if buf.ptr is not None and getattr(buf.prover, "ctx", None):
+                buf.free()
+        self._batch_bufs = {}
         if self.leaf_circuit is not None:
             self.leaf_program.release()
             for c in self.map_circuits:
@@ -503,13 +537,13 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
 
     def __init__(self, prover, poseidon_consts, leaf_headers=8, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), height_varint_bytes=4,
                  field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), defer_commitment=None, device_witness=False,
-                 device_witness_chunk=32):
+                 device_witness_chunk=32, prove_batch=0):
         """defer_commitment (default: leaves of 8 or more headers): the leaves expose their headers' data hashes and the LEVEL-1 NODES hash the
         (height, data_hash) tuples and the leaf subtrees — round 3: an 8-header leaf is 368 compressions x 178 rows = 2.7k rows past 2^16; without
         its 30 tuple / subtree compressions it fits 2^16 rows (half the leaf proof), and the node circuit (75k of 131k rows used) has the room.
         The statement of every node — hence of the root — is unchanged; a chain of ONE leaf has no node and is refused in this mode."""
         super().__init__(prover, poseidon_consts, leaf_blocks=leaf_headers, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
-                         map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk)
+                         map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch)
         self.defer = (leaf_headers >= 8) if defer_commitment is None else bool(defer_commitment)
         if self.defer and leaf_headers & (leaf_headers - 1):
             raise ValueError("deferred tuple hashing needs a power-of-two number of headers per leaf")

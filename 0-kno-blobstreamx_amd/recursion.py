@@ -18,7 +18,7 @@ from array import array
 import numpy as np
 
 from . import (CIRCUIT_POSEIDON_GATE, P, PLONK_NCONST, PLONK_NCONST_SHA, POS_GATE_WIRES, SHA_GATE_WIRES, SHA_ROW_A, SHA_ROW_ADD, SHA_ROW_E,  # noqa: F401
-               SHA_ROW_W, DeviceBuffer, PlonkCircuit)
+               SHA_ROW_W, DeviceBuffer, PlonkCircuit, _ptr)
 
 
 _OP_WORDS = {0: 8, 1: 3, 2: 4, 3: 3, 4: 5, 5: 2, 6: 25, 7: 10, 8: 6, 9: 6, 10: 4, 11: 5, 12: 26, 13: 9, 14: 24}   # words per op (csrc/verify.hip)
@@ -552,14 +552,17 @@ class DeviceWitnessBatch:
             d_idx.free()
             d_out.free()
 
-    def device_witness(self, prover, i, reuse=True):
+    def device_witness(self, prover, i, reuse=True, out=None):
         """placement + row fillers from slab row i, NO host copy of the variables: (wire buffer, public values) like WitnessProgram.device_witness.
         prover: this batch's prover or another ctx on the same device (the map provers of one GPU) — the caller orders the streams: evaluate_device
-        has synchronised its stream before it returned."""
+        has synchronised its stream before it returned.  out: the destination (a DeviceBuffer or a device address with room for W * n words, e.g.
+        one of B matrices side by side for PlonkCircuit.prove_batch_); it is returned in place of a buffer and `reuse` is not consulted."""
         prog = self.program
         n = 1 << prog.log_n
         r = prog._resident(prover)
-        if reuse:
+        if out is not None:
+            dw = out
+        elif reuse:
             if r["wires"] is None or r["wires"].ptr is None:
                 r["wires"] = DeviceBuffer(prover, prog.W * n * 8)
             dw = r["wires"]
@@ -567,10 +570,10 @@ class DeviceWitnessBatch:
             dw = DeviceBuffer(prover, prog.W * n * 8)
         prover.gather(dw, self.row_ptr(i), self.stride, r["cell"], prog.W * n)
         if r["pos"] is not None:
-            prover._chk(prover.lib.glp_poseidon_gate_fill_rows(prover.ctx, dw.ptr, prog.log_n, prog.W, r["pos"].ptr, prog.pos_row_ids.size),
+            prover._chk(prover.lib.glp_poseidon_gate_fill_rows(prover.ctx, _ptr(dw), prog.log_n, prog.W, r["pos"].ptr, prog.pos_row_ids.size),
                         "glp_poseidon_gate_fill_rows")
         if r["sha"] is not None:
-            prover._chk(prover.lib.glp_sha_gate_fill_rows(prover.ctx, dw.ptr, prog.log_n, prog.W, r["sha"].ptr, r["kinds"].ptr, prog.sha_row_ids.size),
+            prover._chk(prover.lib.glp_sha_gate_fill_rows(prover.ctx, _ptr(dw), prog.log_n, prog.W, r["sha"].ptr, r["kinds"].ptr, prog.sha_row_ids.size),
                         "glp_sha_gate_fill_rows")
         if "pub_idx" not in r:
             r["pub_idx"] = prover.to_device(prog.public_vars.astype(np.uint32)) if prog.public_vars.size else None
@@ -1040,16 +1043,19 @@ class WitnessProgram:
             self._dev[id(prover)] = r
         return r
 
-    def device_witness(self, prover, vals, reuse=False):
+    def device_witness(self, prover, vals, reuse=False, out=None):
         """variable values -> wire matrix on the device: the values are uploaded (8 bytes per VARIABLE, not per cell) and placed by the resident
         cell -> variable map (glp_gather_u64), the Poseidon and SHA rows' derived wires filled by the GPU; returns (buffer, public values).
         reuse=True: the buffer is the program's own per-prover wire matrix (valid until the next call for this prover; do not free it) — no device
-        allocation per witness."""
+        allocation per witness.  out: the destination (a DeviceBuffer or a device address with room for W * n words, e.g. one of B matrices side
+        by side for PlonkCircuit.prove_batch_); it is returned in place of a buffer and `reuse` is not consulted."""
         n = 1 << self.log_n
         r = self._resident(prover)
         vals = np.ascontiguousarray(vals, dtype=np.uint64)
         r["src"].upload(np.concatenate((vals, self.fixed_values)) if self.fixed_values.size else vals)
-        if reuse:
+        if out is not None:
+            dw = out
+        elif reuse:
             if r["wires"] is None or r["wires"].ptr is None:
                 r["wires"] = DeviceBuffer(prover, self.W * n * 8)
             dw = r["wires"]
@@ -1057,10 +1063,10 @@ class WitnessProgram:
             dw = DeviceBuffer(prover, self.W * n * 8)
         prover.gather(dw, r["src"], vals.size + self.fixed_values.size, r["cell"], self.W * n)
         if r["pos"] is not None:
-            prover._chk(prover.lib.glp_poseidon_gate_fill_rows(prover.ctx, dw.ptr, self.log_n, self.W, r["pos"].ptr, self.pos_row_ids.size),
+            prover._chk(prover.lib.glp_poseidon_gate_fill_rows(prover.ctx, _ptr(dw), self.log_n, self.W, r["pos"].ptr, self.pos_row_ids.size),
                         "glp_poseidon_gate_fill_rows")
         if r["sha"] is not None:
-            prover._chk(prover.lib.glp_sha_gate_fill_rows(prover.ctx, dw.ptr, self.log_n, self.W, r["sha"].ptr, r["kinds"].ptr, self.sha_row_ids.size),
+            prover._chk(prover.lib.glp_sha_gate_fill_rows(prover.ctx, _ptr(dw), self.log_n, self.W, r["sha"].ptr, r["kinds"].ptr, self.sha_row_ids.size),
                         "glp_sha_gate_fill_rows")
         return dw, [int(v) for v in vals[self.public_vars]]
 

@@ -295,6 +295,34 @@ int glp_plonk_prove_ex(glp_ctx* ctx, glp_plonk_circuit* ck, const uint64_t* d_wi
                        uint32_t pow_bits, uint8_t** proof, size_t* proof_len);
 int glp_plonk_prove(glp_ctx* ctx, glp_plonk_circuit* ck, const uint64_t* d_wire_vals, uint32_t num_queries, uint32_t pow_bits,
                     uint8_t** proof, size_t* proof_len);
+/* B proofs of ONE circuit.  d_wire_vals: B device pointers, each a [n_wires][n] witness (read only; two instances may point at the same
+ * matrix); h_public: [B][n_public] canonical words (NULL when the circuit has none).  proofs[i] / proof_lens[i]: as glp_plonk_prove_ex gives
+ * for instance i alone, BYTE FOR BYTE.  All or nothing: on any error every proofs[i] is NULL, nothing is leaked from the ctx pool, and
+ * glp_last_error names the instance where one is at fault.  B == 0 is GLP_OK and does nothing.  glp_plonk_prove_ex's argument limits
+ * apply; GLP_E_UNSUPPORTED for a B whose launches would exceed 2^31 - 1 workgroups; GLP_E_NOMEM when the pool cannot hold the footprint.
+ * The B transcripts advance in lock-step on the host; every device step is issued once for the whole batch: one gather of the B wire
+ * matrices into a [B*W][n] slab, glp_commit_values_batch (wires), K6 over the batch, glp_commit_values_batch (Z and partial products),
+ * the public-input slab (one inverse NTT, one LDE), K7 (and K7s) over the batch, un-bit-reversal / inverse NTT / unshift of the B*2
+ * quotients, one LDE, glp_merkle_batch, then the batched opening proof (glp_fri_prove_batch's driver on the B challengers).
+ * Whatever B is, the driver's OWN code issues (glp_plonk_last_batch_counts)
+ *   launches     = 1 (wire gather) + 4 (K6: chunk quotients, scan reduce, scan blocks, scan apply) + 1 (K7)
+ *                  + (SHA rows ? 1 : 0) (K7s) + 1 (un-bit-reversal) + 1 (unshift)          = 8, or 9 with SHA rows
+ *   synchronises = 0 — the caps come back with the one synchronise of each of the three commitment calls
+ * and 3 + (n_public ? 1 : 0) + 1 host-to-device copies (descriptor table per stage, public inputs, unshift table).  The NTT, LDE and Merkle
+ * calls and the opening proof are counted by their own plans (glp_merkle_batch_plan, glp_fri_last_batch_counts).
+ * Device footprint, held from the pool until the call returns, in bytes, with n = 2^log_n, N = 8n, W wires, R routed, M = R / 8 and
+ * D = 4 * (2N - 2^cap) digest words per tree:
+ *   8 * B * ( n * (W + 2M) + N * (W + 2M + 2 + 16) + 3 * D )        coefficients and LDEs of the three batches, their digests
+ * plus, transiently, 8 * B * n * (2M + 2) during K6 and 8 * B * (2N + (n_public ? n + N : 0)) during K7, plus the opening proof's own.
+ * A 2^16 x 144 leaf (R = 80) holds 0.60 GB of wire LDE and 0.95 GB in all per instance.
+ * Measured (profiles/plonk_batch.json; the 2^16 x 144 data-commitment leaf, 28 queries, 16 PoW bits, medians of 12 alternating repeats, ms): B sequential
+ * glp_plonk_prove_ex calls against one call here — B = 1: 12.10 / 11.56, B = 2: 24.22 / 19.69, B = 4: 48.43 / 35.56, B = 8: 96.94 / 67.45; every B gains by
+ * more than the baseline's own spread (max - min 0.49 - 2.48 ms).  The Map step of 64 such leaves: 575 ms on three ctxs unbatched, 570 ms on one ctx
+ * and 499 ms on three ctxs with groups of 8. */
+int glp_plonk_prove_batch(glp_ctx* ctx, glp_plonk_circuit* ck, const uint64_t* const* d_wire_vals, const uint64_t* h_public, uint32_t B,
+                          uint32_t num_queries, uint32_t pow_bits, uint8_t** proofs, size_t* proof_lens);
+/* what the PLONK driver's own code issued in the LAST glp_plonk_prove_batch on this ctx: kernel launches and stream synchronises */
+int glp_plonk_last_batch_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
 /* witness generation for Poseidon rows: for each of the n_rows row indices in d_rows (device, u32), wires 12..23 and 25..134 of that row
  * are computed from its wires 0..11 and its swap bit (wire 24), in place in d_wire_vals [n_wires][2^log_n].  Stream-ordered. */
 int glp_poseidon_gate_fill_rows(glp_ctx* ctx, uint64_t* d_wire_vals, uint32_t log_n, uint32_t n_wires, const uint32_t* d_rows,
