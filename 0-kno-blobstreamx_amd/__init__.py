@@ -233,6 +233,13 @@ def load_library():
         "glp_witness_check_words_host": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32,
                                                         _vp, _vp]),
         "glp_gather_u64": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t]),
+        "glp_witness_layout_create": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, ctypes.c_size_t, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                     _vp, ctypes.c_uint32, ctypes.POINTER(_vp), ctypes.c_char_p, ctypes.c_size_t]),
+        "glp_witness_layout_destroy": (None, [_vp]),
+        "glp_witness_layout_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]
+                                    + [ctypes.POINTER(ctypes.c_uint32)] * 3),
+        "glp_witness_place_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_uint32, _vp, ctypes.c_size_t, _vp]),
+        "glp_witness_last_place_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "glp_field_params": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
         "glp_comm_unique_id": (ctypes.c_int, [_vp]),
         "glp_comm_init": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int]),
@@ -952,6 +959,26 @@ class Prover:
     def gather(self, d_dst, d_src, n_src, d_index, n):
         """d_dst[i] = d_src[d_index[i]] (0xFFFFFFFF -> 0), all on the device: witness placement (glp_gather_u64)"""
         self._chk(self.lib.glp_gather_u64(self.ctx, _ptr(d_dst), _ptr(d_src), n_src, _ptr(d_index), n), "glp_gather_u64")
+
+    def witness_place_batch(self, layout, d_values, value_stride, rows, d_wires, wire_stride_words, want_public=True):
+        """B wire matrices side by side from slab rows `rows` of d_values (glp_witness_place_batch: at most 4 launches and 1 synchronise whatever
+        B is).  layout: a glp_witness_layout handle (WitnessProgram.layout()).  Returns the [B][n_public] public values, or None with
+        want_public=False (then the call only enqueues work on this prover's stream)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint32)
+        B = r.size
+        n_pub = ctypes.c_uint32(0)
+        self._chk(self.lib.glp_witness_layout_info(layout, None, None, None, None, None, ctypes.byref(n_pub)), "glp_witness_layout_info")
+        pub = np.zeros((B, n_pub.value), dtype=np.uint64) if want_public else None
+        self._chk(self.lib.glp_witness_place_batch(self.ctx, layout, _ptr(d_values), value_stride, r.ctypes.data if B else None, B, _ptr(d_wires),
+                                                   wire_stride_words, pub.ctypes.data if pub is not None and pub.size else None),
+                  "glp_witness_place_batch")
+        return pub
+
+    def witness_last_place_counts(self):
+        """(launches, stream synchronises) of the last witness_place_batch on this prover"""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        self._chk(self.lib.glp_witness_last_place_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_witness_last_place_counts")
+        return tuple(x.value for x in v)
 
     def ed25519_witness(self, pubs, sigs, msgs):
         """pubs/sigs/msgs: lists of bytes.  Returns [n][37] u64 records (glprover.h)."""

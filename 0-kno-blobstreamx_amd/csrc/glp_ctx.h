@@ -57,6 +57,13 @@ struct glp_ctx {
     uint32_t fri_batch_counts[3] = {0, 0, 0};
     // what the PLONK driver's own code issued in the last glp_plonk_prove_batch: kernel launches, stream synchronises (glp_plonk_last_batch_counts)
     uint32_t plonk_batch_counts[2] = {0, 0};
+    // what the last glp_witness_place_batch issued: kernel launches, stream synchronises (glp_witness_last_place_counts)
+    uint32_t place_counts[2] = {0, 0};
+    // pinned staging of that call's slab-row table (the caller's h_rows may be gone before the copy runs: the call need not synchronise);
+    // place_ev follows the copy, and the next call waits for it before it overwrites the staging
+    uint32_t* place_rows_host = nullptr;
+    size_t place_rows_cap = 0;
+    hipEvent_t place_ev = nullptr;
 };
 
 // stage timing tree of the prover drivers (the TimingTree of the upstream prover, recalled): a

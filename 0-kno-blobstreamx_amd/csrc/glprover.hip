@@ -13,6 +13,7 @@
 #include "glp_ctx.h"
 #include "ntt_exec.h"
 #include "ntt_launch.h"
+#include "place_batch_kernels.cuh"
 
 void glp_set_err(glp_ctx* c, const char* fmt, ...) {
     va_list ap;
@@ -363,6 +364,8 @@ extern "C" void glp_destroy(glp_ctx* c) {
     for (auto& kv : c->pool_live) hipFree(kv.first);             // blocks a driver still held (error paths)
     c->pool_live.clear();
     glp_hash_destroy(c);
+    if (c->place_rows_host) hipHostFree(c->place_rows_host);
+    if (c->place_ev) hipEventDestroy(c->place_ev);
     hipEventDestroy(c->t0);
     hipEventDestroy(c->t1);
     for (int i = 0; i < 2 * GLP_MAX_PASSES; i++) hipEventDestroy(c->pass_ev[i]);
@@ -664,20 +667,7 @@ extern "C" int glp_field_op(glp_ctx* c, int op, const uint64_t* a, const uint64_
     return GLP_OK;
 }
 
-// witness placement: wire cell i takes the variable its index entry names (0xFFFFFFFF = an unused cell, zero)
-__global__ void __launch_bounds__(256) glp_witness_place_kernel(u64* __restrict__ dst, const u64* __restrict__ src, u64 n_src, const u32* __restrict__ index,
-                                                         u64 n, u32* __restrict__ bad) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-        const u32 k = index[i];
-        u64 v = 0;
-        if (k != 0xFFFFFFFFu) {
-            if (k < n_src) v = src[k];
-            else atomicOr(bad, 1u);
-        }
-        dst[i] = v;
-    }
-}
-
+// witness placement (the kernel: place_batch_kernels.cuh, beside its batched form)
 extern "C" int glp_gather_u64(glp_ctx* c, uint64_t* d_dst, const uint64_t* d_src, size_t n_src, const uint32_t* d_index, size_t n) {
     if (!c) return GLP_E_INVALID;
     GLP_BIND(c);
@@ -688,7 +678,7 @@ extern "C" int glp_gather_u64(glp_ctx* c, uint64_t* d_dst, const uint64_t* d_src
     GLP_HIPCHK(c, hipMemsetAsync(flag.p, 0, 4, c->stream));
     u64 blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(glp_witness_place_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_dst, d_src, (u64)n_src, d_index, (u64)n, (u32*)flag.p);
+    hipLaunchKernelGGL(glp_witness_place_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_dst, d_src, (u64)n_src, d_index, (u64)n, (u32*)flag.p);
     GLP_HIPCHK(c, hipGetLastError());
     u32 bad = 0;
     GLP_HIPCHK(c, hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, c->stream));

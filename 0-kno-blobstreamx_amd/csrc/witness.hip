@@ -6,9 +6,13 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <new>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include "glp_ctx.h"
 #include "hash_state.h"
 #include "witness_kernels.cuh"
+#include "place_batch_kernels.cuh"
 
 struct glp_witness_plan {
     glp_wit_compiled c;
@@ -223,5 +227,216 @@ extern "C" int glp_witness_check_words(glp_ctx* c, const uint64_t* d_values, siz
     GLP_HIPCHK(c, hipMemcpyAsync(host.data(), d_bad, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
     GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
     for (u32 b = 0; b < B; b++) { h_first_bad_var[b] = host[b]; h_first_bad_bits[b] = host[B + b]; }
+    return GLP_OK;
+}
+
+// ---- batched witness placement ------------------------------------------------------------------------------------------------------------
+// The LAYOUT of a recorded circuit: how the evaluated variables (and the fixed values behind them) become a wire matrix.  Host arrays, every
+// index checked once in glp_witness_layout_create — the kernels of place_batch_kernels.cuh carry no flag.  OWNERSHIP of the device copy as for
+// the plan above: uploaded on the first glp_witness_place_batch per DEVICE, shared by the ctxs of that device, freed by
+// glp_witness_layout_destroy.
+struct glp_witness_layout {
+    u32 log_n = 0, W = 0;
+    u64 n_src = 0;
+    std::vector<u32> cell, pos_rows, sha_rows, sha_kinds, public_vars;
+    struct Resident { u32* cell; u32* pos_rows; u32* sha_rows; u32* sha_kinds; u32* public_vars; };
+    std::map<int, Resident> dev;
+    std::mutex mu;
+};
+
+static int layout_refuse(char* err, size_t err_len, const char* fmt, ...) {
+    if (err && err_len) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(err, err_len, fmt, ap);
+        va_end(ap);
+    }
+    return GLP_E_INVALID;
+}
+
+extern "C" int glp_witness_layout_create(uint32_t log_n, uint32_t n_wires, const uint32_t* cell_index, size_t n_src, const uint32_t* pos_rows,
+                                         uint32_t n_pos_rows, const uint32_t* sha_rows, const uint32_t* sha_kinds, uint32_t n_sha_rows,
+                                         const uint32_t* public_vars, uint32_t n_public, glp_witness_layout** layout, char* err, size_t err_len) {
+    if (err && err_len) err[0] = 0;
+    if (!layout) return GLP_E_INVALID;
+    *layout = nullptr;
+    if (log_n > 24 || n_wires == 0 || n_wires > 4096 || !cell_index || (!pos_rows && n_pos_rows) || ((!sha_rows || !sha_kinds) && n_sha_rows) ||
+        (!public_vars && n_public))
+        return layout_refuse(err, err_len, "glp_witness_layout_create: bad argument (log_n <= 24, 1 <= n_wires <= 4096, no null array with a non-zero count)");
+    if ((u64)n_src >= 0xFFFFFFFFull) {
+        layout_refuse(err, err_len, "glp_witness_layout_create: n_src = %zu does not fit the 32-bit cell index", n_src);
+        return GLP_E_UNSUPPORTED;
+    }
+    const u64 n = 1ull << log_n, cells = (u64)n_wires * n;
+    if (n_pos_rows && n_wires < GLP_POS_GATE_WIRES)
+        return layout_refuse(err, err_len, "glp_witness_layout_create: %u wires, a Poseidon row needs %d", n_wires, (int)GLP_POS_GATE_WIRES);
+    if (n_sha_rows && n_wires < GLP_SHA_GATE_WIRES)
+        return layout_refuse(err, err_len, "glp_witness_layout_create: %u wires, a SHA row needs %d", n_wires, (int)GLP_SHA_GATE_WIRES);
+    for (u64 i = 0; i < cells; i++)
+        if (cell_index[i] != 0xFFFFFFFFu && cell_index[i] >= n_src)
+            return layout_refuse(err, err_len, "glp_witness_layout_create: cell %llu (wire %llu, row %llu) names source %u of %zu", (unsigned long long)i,
+                                 (unsigned long long)(i >> log_n), (unsigned long long)(i & (n - 1)), cell_index[i], n_src);
+    for (u32 k = 0; k < n_pos_rows; k++)
+        if (pos_rows[k] >= n) return layout_refuse(err, err_len, "glp_witness_layout_create: Poseidon row entry %u is row %u of %llu", k, pos_rows[k], (unsigned long long)n);
+    for (u32 k = 0; k < n_sha_rows; k++) {
+        if (sha_rows[k] >= n) return layout_refuse(err, err_len, "glp_witness_layout_create: SHA row entry %u is row %u of %llu", k, sha_rows[k], (unsigned long long)n);
+        if (sha_kinds[k] > 3) return layout_refuse(err, err_len, "glp_witness_layout_create: SHA row entry %u has kind %u (0..3)", k, sha_kinds[k]);
+    }
+    for (u32 k = 0; k < n_public; k++)
+        if (public_vars[k] >= n_src) return layout_refuse(err, err_len, "glp_witness_layout_create: public input %u names source %u of %zu", k, public_vars[k], n_src);
+    glp_witness_layout* L = new (std::nothrow) glp_witness_layout();
+    if (!L) return GLP_E_NOMEM;
+    try {
+        L->log_n = log_n; L->W = n_wires; L->n_src = n_src;
+        L->cell.assign(cell_index, cell_index + cells);
+        L->pos_rows.assign(pos_rows, pos_rows + n_pos_rows);
+        L->sha_rows.assign(sha_rows, sha_rows + n_sha_rows);
+        L->sha_kinds.assign(sha_kinds, sha_kinds + n_sha_rows);
+        L->public_vars.assign(public_vars, public_vars + n_public);
+    } catch (const std::bad_alloc&) {
+        delete L;
+        return GLP_E_NOMEM;
+    }
+    *layout = L;
+    return GLP_OK;
+}
+
+extern "C" void glp_witness_layout_destroy(glp_witness_layout* L) {
+    if (!L) return;
+    int cur = 0;
+    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+    for (auto& kv : L->dev) {
+        if (hipSetDevice(kv.first) != hipSuccess) continue;
+        hipFree(kv.second.cell); hipFree(kv.second.pos_rows); hipFree(kv.second.sha_rows); hipFree(kv.second.sha_kinds); hipFree(kv.second.public_vars);
+    }
+    if (have_cur && !L->dev.empty()) hipSetDevice(cur);
+    delete L;
+}
+
+extern "C" int glp_witness_layout_info(const glp_witness_layout* L, uint32_t* log_n, uint32_t* n_wires, uint64_t* n_src, uint32_t* n_pos_rows,
+                                       uint32_t* n_sha_rows, uint32_t* n_public) {
+    if (!L) return GLP_E_INVALID;
+    if (log_n) *log_n = L->log_n;
+    if (n_wires) *n_wires = L->W;
+    if (n_src) *n_src = L->n_src;
+    if (n_pos_rows) *n_pos_rows = (u32)L->pos_rows.size();
+    if (n_sha_rows) *n_sha_rows = (u32)L->sha_rows.size();
+    if (n_public) *n_public = (u32)L->public_vars.size();
+    return GLP_OK;
+}
+
+extern "C" int glp_witness_last_place_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs) {
+    if (!c) return GLP_E_INVALID;
+    if (n_launches) *n_launches = c->place_counts[0];
+    if (n_host_syncs) *n_host_syncs = c->place_counts[1];
+    return GLP_OK;
+}
+
+constexpr u64 PLACE_MAX_BLOCKS = 0x7fffffffull;
+
+extern "C" int glp_witness_place_batch(glp_ctx* c, const glp_witness_layout* layout_c, const uint64_t* d_values, size_t value_stride,
+                                       const uint32_t* h_rows, uint32_t B, uint64_t* d_wires, size_t wire_stride_words, uint64_t* h_public) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->place_counts[0] = c->place_counts[1] = 0;
+    if (B == 0) return GLP_OK;
+    glp_witness_layout* L = const_cast<glp_witness_layout*>(layout_c);
+    if (!L || !d_values || !h_rows || !d_wires) { glp_set_err(c, "glp_witness_place_batch: bad argument"); return GLP_E_INVALID; }
+    const u64 n = 1ull << L->log_n, cells = (u64)L->W * n;
+    if (value_stride < L->n_src || wire_stride_words < cells) {
+        glp_set_err(c, "glp_witness_place_batch: value_stride must be >= the layout's n_src (%llu) and wire_stride_words >= n_wires * n (%llu)",
+                    (unsigned long long)L->n_src, (unsigned long long)cells);
+        return GLP_E_INVALID;
+    }
+    const u32 n_pos = (u32)L->pos_rows.size(), n_sha = (u32)L->sha_rows.size(), n_pub = (u32)L->public_vars.size();
+    const u32 bpi_pos = (n_pos + 63) / 64, bpi_sha = (n_sha + 63) / 64;
+    if ((u64)B * bpi_pos > PLACE_MAX_BLOCKS || (u64)B * bpi_sha > PLACE_MAX_BLOCKS) {
+        glp_set_err(c, "glp_witness_place_batch: B = %u is more than one call takes at this size (a launch of more than 2^31 - 1 workgroups)", B);
+        return GLP_E_UNSUPPORTED;
+    }
+    glp_hash_state* h = nullptr;
+    if (n_pos) {
+        h = glp_hash_get(c);
+        if (!h->have_consts) { glp_set_err(c, "glp_witness_place_batch: Poseidon constants not set"); return GLP_E_STATE; }
+    }
+    glp_witness_layout::Resident res;
+    {
+        std::lock_guard<std::mutex> g(L->mu);
+        auto it = L->dev.find(c->device);
+        if (it == L->dev.end()) {
+            glp_witness_layout::Resident r{};
+            hipError_t e = upload_vec(L->cell, &r.cell);                       // blocking copies: resident before any stream can use it
+            if (e == hipSuccess) e = upload_vec(L->pos_rows, &r.pos_rows);
+            if (e == hipSuccess) e = upload_vec(L->sha_rows, &r.sha_rows);
+            if (e == hipSuccess) e = upload_vec(L->sha_kinds, &r.sha_kinds);
+            if (e == hipSuccess) e = upload_vec(L->public_vars, &r.public_vars);
+            if (e != hipSuccess) {
+                hipFree(r.cell); hipFree(r.pos_rows); hipFree(r.sha_rows); hipFree(r.sha_kinds); hipFree(r.public_vars);
+                glp_set_err(c, "glp_witness_place_batch: uploading the layout: %s", hipGetErrorString(e));
+                return e == hipErrorOutOfMemory ? GLP_E_NOMEM : GLP_E_HIP;
+            }
+            it = L->dev.emplace(c->device, r).first;
+        }
+        res = it->second;
+    }
+    // the slab-row table: through pinned staging of the ctx, so that the copy is asynchronous and the caller's h_rows is done with on return
+    if (!c->place_ev) GLP_HIPCHK(c, hipEventCreateWithFlags(&c->place_ev, hipEventDisableTiming));
+    else GLP_HIPCHK(c, hipEventSynchronize(c->place_ev));                     // the previous call's 4 * B-byte copy: long done unless calls follow back to back
+    if (c->place_rows_cap < B) {
+        if (c->place_rows_host) { hipHostFree(c->place_rows_host); c->place_rows_host = nullptr; c->place_rows_cap = 0; }
+        const size_t cap = B < 64 ? 64 : (size_t)B;
+        if (hipHostMalloc((void**)&c->place_rows_host, cap * 4, hipHostMallocDefault) != hipSuccess) {
+            c->place_rows_host = nullptr;
+            glp_set_err(c, "glp_witness_place_batch: no pinned staging for %u slab rows", B);
+            return GLP_E_NOMEM;
+        }
+        c->place_rows_cap = cap;
+    }
+    memcpy(c->place_rows_host, h_rows, (size_t)B * 4);
+    const bool want_public = h_public && n_pub;
+    const size_t pub_bytes = want_public ? (size_t)B * n_pub * 8 : 0;
+    GlpPoolBuf tmp(c);                                                          // [B * n_public] public values, then [B] slab rows
+    if (tmp.alloc(pub_bytes + (size_t)B * 4 + 16) != hipSuccess) return GLP_E_NOMEM;
+    u64* d_pub = tmp.u();
+    u32* d_rows = (u32*)((unsigned char*)tmp.p + pub_bytes);
+    GLP_HIPCHK(c, hipMemcpyAsync(d_rows, c->place_rows_host, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
+    GLP_HIPCHK(c, hipEventRecord(c->place_ev, c->stream));
+    u32 launches = 0;
+    {
+        const u64 want = (cells + 255) / 256;
+        const u32 grid = (u32)(want < 4096 ? want : 4096);
+        hipLaunchKernelGGL(glp_witness_place_batch_kernel<0>, dim3(grid), dim3(256), 0, c->stream, d_wires, (u64)wire_stride_words, d_values, (u64)value_stride,
+                           d_rows, B, res.cell, cells);
+        GLP_HIPCHK(c, hipGetLastError());
+        launches++;
+    }
+    if (n_pos) {
+        if (h->small_mds && !getenv("GLP_K7_GENERIC_MDS"))                      // the choice glp_poseidon_gate_fill_rows makes
+            hipLaunchKernelGGL(glp_poseidon_gate_fill_batch_kernel<1>, dim3(B * bpi_pos), dim3(64), 0, c->stream, d_wires, (u64)wire_stride_words, n,
+                               res.pos_rows, n_pos, bpi_pos, h->d_consts);
+        else
+            hipLaunchKernelGGL(glp_poseidon_gate_fill_batch_kernel<0>, dim3(B * bpi_pos), dim3(64), 0, c->stream, d_wires, (u64)wire_stride_words, n,
+                               res.pos_rows, n_pos, bpi_pos, h->d_consts);
+        GLP_HIPCHK(c, hipGetLastError());
+        launches++;
+    }
+    if (n_sha) {
+        hipLaunchKernelGGL(glp_sha_gate_fill_batch_kernel<0>, dim3(B * bpi_sha), dim3(64), 0, c->stream, d_wires, (u64)wire_stride_words, n, res.sha_rows,
+                           res.sha_kinds, n_sha, bpi_sha);
+        GLP_HIPCHK(c, hipGetLastError());
+        launches++;
+    }
+    c->place_counts[0] = launches;
+    if (want_public) {
+        const u64 want = ((u64)B * n_pub + 255) / 256;
+        const u32 grid = (u32)(want < 4096 ? want : 4096);
+        hipLaunchKernelGGL(glp_witness_public_batch_kernel<0>, dim3(grid), dim3(256), 0, c->stream, d_pub, d_values, (u64)value_stride, d_rows, B,
+                           res.public_vars, n_pub);
+        GLP_HIPCHK(c, hipGetLastError());
+        c->place_counts[0] = ++launches;
+        GLP_HIPCHK(c, hipMemcpyAsync(h_public, d_pub, pub_bytes, hipMemcpyDeviceToHost, c->stream));
+        GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->place_counts[1] = 1;
+    }
     return GLP_OK;
 }

@@ -60,6 +60,17 @@ def _combine(b, outs):
     return roots[0] + digs[0]
 
 
+def _rebase_instance(msg, lo, single):
+    """a refusal raised for a run of nodes that starts at position `lo` of its level: 'instance k: ...' becomes 'instance lo + k: ...'; the
+    refusal of a run of ONE node carries no instance number and gets 'instance lo: '"""
+    if single:
+        return f"instance {lo}: {msg}"
+    if msg.startswith("instance "):
+        k, rest = msg[len("instance "):].split(":", 1)
+        return f"instance {lo + int(k)}:{rest}"
+    return msg
+
+
 class DataCommitmentMapReduce:
     """prove_range(heights, data_roots) -> one proof for the whole range; verify(...) checks it against the tuples.  leaf_blocks and fan_in are
     powers of two; the number of leaves must be fan_in^k * m with the last level's fan-in m a power of two <= fan_in (e.g. 64 leaves, fan_in 16:
@@ -98,7 +109,17 @@ class DataCommitmentMapReduce:
         device), so that no host evaluator runs anywhere.
         prove_batch (default 0: one prover call per leaf): with k > 0 every prover of the Map step places contiguous groups of up to k leaves of
         its share side by side in a [k][W][n] buffer of its own (allocated once) and proves each group with ONE PlonkCircuit.prove_batch_ call:
-        the same proofs, byte for byte.  The Reduce levels are not batched."""
+        the same proofs, byte for byte.  With device_witness the k matrices of a group are placed by ONE call
+        (DeviceWitnessBatch.device_witness_batch), not k.
+        The Reduce does the same with every level of at least two nodes: the level's nodes are cut into contiguous groups of up to k, the groups
+        go round robin to the main prover and the node's replicas on the map provers, and each group is ONE RecursionProgram.prove_batch /
+        prove_placed call into that worker's own group buffer (allocated once per (prover, node circuit)).  Levels of one node, the padded root
+        and outer circuits of the subclasses go through prove as before.  Measured on one MI355X with three provers the batched Reduce is NOT
+        faster than the unbatched one (within the noise at k = 2 and 4, 25 % slower at k = 8 over 8 nodes, where one run takes the
+        whole level to one prover): it is opt-in, for hosts that drive one prover per GPU.
+        Memory: a group of k nodes of 2^17 x 144 holds k * 151 MB of wires.
+        The batched prover holds k * 1.2 GB of wire LDE per prover on top of that (GLP_E_UNSUPPORTED from glp_plonk_prove_batch is the only hard
+        limit)."""
         assert leaf_blocks >= 1 and leaf_blocks & (leaf_blocks - 1) == 0 and fan_in >= 2 and fan_in & (fan_in - 1) == 0
         self.prover, self.consts = prover, tuple(np.ascontiguousarray(a, dtype=np.uint64) for a in poseidon_consts)
         self.map_provers, self.map_circuits = list(map_provers), []
@@ -110,15 +131,16 @@ class DataCommitmentMapReduce:
         self.device_witness, self.device_witness_chunk = bool(device_witness), max(1, int(device_witness_chunk))
         self.prove_batch, self._batch_bufs = max(0, int(prove_batch)), {}
 
-    def _prove_group(self, prover, circuit, place, count):
+    def _prove_group(self, prover, circuit, place, count, place_all=None):
         """one prove_batch_ call for `count` <= prove_batch leaves: place(j, address) lays leaf j's wire matrix at that address of this prover's
-        [k][W][n] buffer and returns its public values; returns the proofs in order"""
+        [k][W][n] buffer and returns its public values — or place_all(address) lays all `count` matrices side by side from there in one call and
+        returns the list of their public values; returns the proofs in order"""
         words = self.leaf_program.W << self.leaf_program.log_n
         buf = self._batch_bufs.get(id(prover))
         if buf is None or buf.ptr is None or buf.prover is not prover:
             buf = self._batch_bufs[id(prover)] = DeviceBuffer(prover, self.prove_batch * words * 8)
         addrs = [buf.ptr + j * words * 8 for j in range(count)]
-        publics = [place(j, addrs[j]) for j in range(count)]
+        publics = place_all(buf.ptr) if place_all is not None else [place(j, addrs[j]) for j in range(count)]
         return circuit.prove_batch_(addrs, publics, self.nq, self.pw)
 
     # ---- Map ----------------------------------------------------------------------------------------------------------------------
@@ -224,8 +246,8 @@ class DataCommitmentMapReduce:
                     if self.prove_batch:
                         for g in range(0, len(share), self.prove_batch):
                             ids = share[g:g + self.prove_batch]
-                            place = lambda j, addr, ids=ids: slab.device_witness(prover, ids[j], out=addr)[1]
-                            for i, proof in zip(ids, self._prove_group(prover, circuit, place, len(ids))):
+                            place_all = lambda addr, ids=ids: slab.device_witness_batch(prover, ids, addr)
+                            for i, proof in zip(ids, self._prove_group(prover, circuit, None, len(ids), place_all=place_all)):
                                 out[lo + i] = proof
                         return
                     for i in share:
@@ -282,6 +304,9 @@ class DataCommitmentMapReduce:
             if getattr(self, "device_witness", False):
                 done = self._reduce_level_device(rp, groups)
                 nxt, public = [d[0] for d in done], done[-1][1]
+            elif len(groups) > 1 and getattr(self, "prove_batch", 0):
+                done = self._reduce_level_batched(rp, groups)
+                nxt, public = [d[0] for d in done], done[-1][1]
             elif len(groups) > 1 and self.map_provers:
                 # several nodes of one level: one host thread per prover, each with its own commitment of the level's (shared) recording
                 from concurrent.futures import ThreadPoolExecutor
@@ -314,16 +339,63 @@ class DataCommitmentMapReduce:
                 return nxt[0], public, key, level
             cur = nxt
 
-    def _reduce_level_device(self, rp, groups):
-        """the nodes of one level with their witnesses made on the device: device_witness_chunk groups at a time through rp.witness_batch on the
-        main prover (which returns with its stream synchronised), then every prover — the main one and, for several groups, rp's replicas on the
-        map provers — places and proves its share of the chunk from the slab, as _map_inputs_device does for leaves.  [(proof, public)] in order."""
-        from concurrent.futures import ThreadPoolExecutor
+    def _level_workers(self, rp, groups):
+        """the provers of one level: rp and, for several groups, its replicas on the map provers (committed once per node circuit)"""
         workers = [rp]
         if len(groups) > 1 and self.map_provers:
             if id(rp) not in self.node_replicas:
                 self.node_replicas[id(rp)] = [rp.replicate(p) for p in self.map_provers]
             workers += self.node_replicas[id(rp)]
+        return workers
+
+    def _reduce_level_batched(self, rp, groups):
+        """the nodes of one level (at least two) with prove_batch = k > 0 and host witnesses: contiguous runs of up to k nodes, run j on worker
+        j mod (number of workers), each run ONE RecursionProgram.prove_batch call into that worker's group buffer.  [(proof, public)] in order.
+        A refused child raises prove's text with the node's position in the level ('instance i: ...') and nothing is returned."""
+        from concurrent.futures import ThreadPoolExecutor
+        workers = self._level_workers(rp, groups)
+        k = self.prove_batch
+        runs = [(lo, groups[lo:lo + k]) for lo in range(0, len(groups), k)]
+        out = [None] * len(groups)
+
+        def work(w):
+            if w:
+                self.map_provers[w - 1].bind_thread()
+            for lo, run in runs[w::len(workers)]:
+                try:
+                    done = workers[w].prove_batch(run, self.nq, self.pw)
+                except ValueError as e:
+                    raise ValueError(_rebase_instance(str(e), lo, len(run) == 1)) from None
+                out[lo:lo + len(run)] = done
+        n_active = min(len(workers), len(runs))
+        if n_active == 1:
+            work(0)
+        else:
+            with ThreadPoolExecutor(n_active - 1) as ex:
+                futs = [ex.submit(work, w) for w in range(1, n_active)]
+                err = None
+                try:
+                    work(0)
+                except ValueError as e:
+                    err = e
+                for f in futs:
+                    try:
+                        f.result()
+                    except ValueError as e:
+                        err = err or e
+                if err is not None:
+                    raise err
+        return out
+
+    def _reduce_level_device(self, rp, groups):
+        """the nodes of one level with their witnesses made on the device: device_witness_chunk groups at a time through rp.witness_batch on the
+        main prover (which returns with its stream synchronised), then every prover — the main one and, for several groups, rp's replicas on the
+        map provers — places and proves its share of the chunk from the slab, as _map_inputs_device does for leaves.  [(proof, public)] in order.
+        With prove_batch = k > 0 and at least two groups a worker's share is contiguous runs of up to k nodes of the chunk (run j on worker j mod
+        the number of workers), each ONE placement call and ONE prover call (RecursionProgram.prove_placed)."""
+        from concurrent.futures import ThreadPoolExecutor
+        workers = self._level_workers(rp, groups)
+        batch = getattr(self, "prove_batch", 0) if len(groups) > 1 else 0
         n_workers, chunk = len(workers), self.device_witness_chunk
         out = [None] * len(groups)
         pool = ThreadPoolExecutor(n_workers - 1) if n_workers > 1 else None
@@ -342,6 +414,11 @@ class DataCommitmentMapReduce:
                 def work(w, lo=lo, part=part, slab=slab):
                     if w:
                         self.map_provers[w - 1].bind_thread()
+                    if batch:
+                        runs = [range(r, min(r + batch, len(part))) for r in range(0, len(part), batch)]
+                        for run in runs[w::n_workers]:
+                            out[lo + run[0]:lo + run[0] + len(run)] = workers[w].prove_placed(slab, run, self.nq, self.pw)
+                        return
                     for i in range(w, len(part), n_workers):
                         dw, public = slab.device_witness(workers[w].prover, i, reuse=True)
                         out[lo + i] = (workers[w].circuit.prove_(dw, self.nq, self.pw, public=public), public)
@@ -432,6 +509,7 @@ class DataCommitmentMapReduce:
     def free(self):
         for reps in self.node_replicas.values():
             for rp in reps:
+                rp.free_group_buffer()
                 rp.circuit.free()
         self.node_replicas = {}
         for rp in self.nodes.values():

@@ -584,6 +584,22 @@ class DeviceWitnessBatch:
             public = [int(v) for v in r["pub_out"].download(prog.public_vars.size)]
         return dw, public
 
+    def device_witness_batch(self, prover, ids, out, want_public=True):
+        """device_witness for SEVERAL slab rows in one call (glp_witness_place_batch): the wire matrices of instances `ids` (any order, repeats
+        allowed) side by side in `out`, a [len(ids)][W][n] DeviceBuffer or device address — the layout PlonkCircuit.prove_batch_ is handed.  At
+        most 4 launches and 1 stream synchronise whatever len(ids) is, against 2-4 launches and 2 synchronises PER INSTANCE through
+        device_witness; every word is the same.  Returns the list of public-value lists (None with want_public=False: nothing is synchronised).
+        prover: as for device_witness."""
+        prog = self.program
+        ids = [int(i) for i in ids]
+        for i in ids:
+            self.row_ptr(i)
+        words = prog.W << prog.log_n
+        if isinstance(out, DeviceBuffer) and out.nbytes < len(ids) * words * 8:
+            raise ValueError(f"the destination holds {out.nbytes} bytes, {len(ids)} wire matrices need {len(ids) * words * 8}")
+        pub = prover.witness_place_batch(prog.layout(), self.buf.ptr, self.stride, ids, out, words, want_public=want_public)
+        return None if pub is None else [[int(v) for v in row] for row in pub]
+
     def download(self, i):
         """the variables of instance i on the host (tests, debugging)"""
         self.row_ptr(i)
@@ -1070,8 +1086,40 @@ class WitnessProgram:
                         "glp_sha_gate_fill_rows")
         return dw, [int(v) for v in vals[self.public_vars]]
 
+    def layout(self):
+        """the placement layout as the C ABI takes it (glp_witness_layout_create: the cell -> variable map, the source count n_values + fixed
+        values, the Poseidon / SHA row lists, the public variables; every index checked there, once).  Host work, no GPU; cached, not part of
+        save / load.  The copy a device holds after the first DeviceWitnessBatch.device_witness_batch there is shared by the provers of that
+        device and lives until release() (no argument) or until this object goes."""
+        import ctypes
+        import weakref
+        lay = self.__dict__.get("_layout")
+        if lay is None:
+            from . import load_library
+            lib = load_library()
+            pub = np.ascontiguousarray(self.public_vars, dtype=np.int64)
+            if pub.size and (pub.min() < 0 or pub.max() >= 0xFFFFFFFF):
+                raise ValueError("not a recorded circuit of this format")
+            cell, pos, sha, kinds, pub = (np.ascontiguousarray(a, dtype=np.uint32) for a in (self.cell_index, self.pos_row_ids, self.sha_row_ids, self.sha_kinds, pub))
+            if sha.size != kinds.size or cell.size != self.W << self.log_n:
+                raise ValueError("not a recorded circuit of this format")
+            h, err = ctypes.c_void_p(), ctypes.create_string_buffer(256)
+            rc = lib.glp_witness_layout_create(self.log_n, self.W, cell.ctypes.data, self.n_values + self.fixed_values.size, pos.ctypes.data if pos.size else None,
+                                               pos.size, sha.ctypes.data if sha.size else None, kinds.ctypes.data if sha.size else None, sha.size,
+                                               pub.ctypes.data if pub.size else None, pub.size, ctypes.byref(h), err, len(err))
+            if rc != 0:
+                raise ValueError(f"not a recorded circuit of this format ({err.value.decode() or rc})")
+            lay = self._layout = h.value
+            fin = weakref.finalize(self, lib.glp_witness_layout_destroy, ctypes.c_void_p(lay))
+            fin.atexit = False          # as for the plan: at interpreter exit the driver frees the device copy
+            self._layout_finalizer = fin
+        return lay
+
     def release(self, prover=None):
-        """free what is resident (for one prover, or all)"""
+        """free what is resident (for one prover, or all); with no argument also the placement layout and its device copies"""
+        if prover is None and self.__dict__.get("_layout") is not None:
+            self._layout = None
+            self.__dict__.pop("_layout_finalizer")()          # calls glp_witness_layout_destroy now, once
         for key in [k for k in self._dev if prover is None or k == id(prover)]:
             for buf in self._dev.pop(key).values():
                 if buf is not None and buf.ptr is not None and getattr(buf.prover, "ctx", None):

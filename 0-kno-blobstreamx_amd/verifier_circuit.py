@@ -793,7 +793,65 @@ class RecursionProgram:
             dw, public = self.witness(proofs, reuse=True)
         return self.circuit.prove_(dw, num_queries, pow_bits, public=public), public
 
+    def _group_buffer(self, count):
+        """this object's [count][W][n] buffer of wire matrices side by side, on its prover: allocated once and kept (hipMalloc synchronises the
+        whole device, see WitnessProgram._resident), grown only when a larger group arrives"""
+        from . import DeviceBuffer
+        need = count * (self.program.W << self.program.log_n) * 8
+        buf = self.__dict__.get("_batch_buf")
+        if buf is None or buf.ptr is None or buf.prover is not self.prover or buf.nbytes < need:
+            self.free_group_buffer()
+            buf = self._batch_buf = DeviceBuffer(self.prover, need)
+        return buf
+
+    def free_group_buffer(self):
+        buf = self.__dict__.pop("_batch_buf", None)
+        if buf is not None and buf.ptr is not None and getattr(buf.prover, "ctx", None):
+            buf.free()
+
+    def prove_placed(self, slab, ids, num_queries=28, pow_bits=16):
+        """[(proof, public)] for the rows `ids` of an evaluated and checked slab (witness_batch of this program, made on this prover or on another
+        ctx of the same device): ONE placement call (DeviceWitnessBatch.device_witness_batch) into this object's group buffer, then ONE
+        PlonkCircuit.prove_batch_ — each proof byte for byte what prove gives for that group alone."""
+        ids = list(ids)
+        if not ids:
+            return []
+        words = self.program.W << self.program.log_n
+        buf = self._group_buffer(len(ids))
+        publics = slab.device_witness_batch(self.prover, ids, buf)
+        proofs = self.circuit.prove_batch_([buf.ptr + j * words * 8 for j in range(len(ids))], publics, num_queries, pow_bits)
+        return list(zip(proofs, publics))
+
+    def prove_batch(self, groups, num_queries=28, pow_bits=16, device_witness=False):
+        """prove for SEVERAL batches of proofs (the nodes of a Reduce level) with ONE prover call: [(proof, public)] in order, each what
+        prove(group) returns, byte for byte.  device_witness: witness_batch(groups), then prove_placed.  Otherwise the host evaluator and
+        check_words per group as in witness(), each matrix placed into its slot of the group buffer (WitnessProgram.device_witness(out=)), then
+        one PlonkCircuit.prove_batch_.  A refused child raises the text prove raises — prefixed with 'instance i: ' when there are several
+        groups — before anything is proved: no proof is returned.
+        Memory: a group of k nodes of 2^17 x 144 holds k * 151 MB of wires in the group buffer.
+        The batched prover holds k * 1.2 GB of wire LDE per prover on top of that (glp_plonk_prove_batch's footprint; GLP_E_UNSUPPORTED from
+        there is the only hard limit on k)."""
+        groups = list(groups)
+        if not groups:
+            return []
+        if device_witness:
+            return self.prove_placed(self.witness_batch(groups), range(len(groups)), num_queries, pow_bits)
+        words = self.program.W << self.program.log_n
+        buf = self._group_buffer(len(groups))
+        addrs = [buf.ptr + j * words * 8 for j in range(len(groups))]
+        publics = []
+        for i, proofs in enumerate(groups):
+            try:
+                inputs, ws = self.program.inputs_from_words(proofs)
+                vals = self.program.evaluate(self.consts, inputs)
+                self.program.check_words(vals, ws)
+            except ValueError as e:
+                raise ValueError((f"instance {i}: " if len(groups) > 1 else "") + str(e)) from None
+            publics.append(self.program.device_witness(self.prover, vals, out=addrs[i])[1])
+        return list(zip(self.circuit.prove_batch_(addrs, publics, num_queries, pow_bits), publics))
+
     def free(self):
+        self.free_group_buffer()
         slab = self.__dict__.pop("_slab", None)
         if slab is not None:
             slab.free()

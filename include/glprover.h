@@ -455,6 +455,46 @@ int glp_witness_check_words(glp_ctx* ctx, const uint64_t* d_values, size_t value
 int glp_witness_check_words_host(const uint64_t* values, size_t value_stride, uint32_t B, const uint32_t* var_idx, const uint64_t* var_want,
                                  uint32_t n_var, const uint32_t* bit_vars, const uint32_t* bit_start, const uint64_t* bit_want, uint32_t n_bits,
                                  uint64_t* first_bad_var, uint64_t* first_bad_bits);
+/* Batched witness placement.  A LAYOUT holds the host arrays that say how a recorded circuit's evaluated variables become a wire matrix
+ * [n_wires][2^log_n]: cell_index [n_wires * n] (cell -> source word; 0xFFFFFFFF = an unused cell, zero), n_src (the variables plus the fixed
+ * values appended behind them: the words of one slab row that cells may name), the Poseidon rows, the SHA rows with their kinds (GLP_SHA_ROW_*)
+ * and the variables that are the public inputs.  glp_witness_layout_create is host-only (no ctx, no GPU) and does EVERY range check once:
+ * a cell entry is < n_src or the unused marker, a row is < n, a kind is <= 3, n_wires >= GLP_POS_GATE_WIRES when there are Poseidon rows and
+ * >= GLP_SHA_GATE_WIRES when there are SHA rows, a public variable is < n_src: GLP_E_INVALID with the reason in err (may be NULL) for a
+ * violation, GLP_E_UNSUPPORTED for n_src >= 2^32 - 1.  The placement kernels therefore carry no "bad index" flag and copy nothing back.
+ * The arrays are copied.  The device copy is uploaded on the first glp_witness_place_batch per DEVICE and owned by the layout: shared by every
+ * ctx of that device, freed by glp_witness_layout_destroy (not by glp_destroy) — destroy it when no call that uses it is running and the
+ * streams that ran one have been synchronised. */
+typedef struct glp_witness_layout glp_witness_layout;
+int glp_witness_layout_create(uint32_t log_n, uint32_t n_wires, const uint32_t* cell_index, size_t n_src, const uint32_t* pos_rows,
+                              uint32_t n_pos_rows, const uint32_t* sha_rows, const uint32_t* sha_kinds, uint32_t n_sha_rows,
+                              const uint32_t* public_vars, uint32_t n_public, glp_witness_layout** layout, char* err, size_t err_len);
+void glp_witness_layout_destroy(glp_witness_layout* layout);
+/* what the layout was made with; any output pointer may be NULL */
+int glp_witness_layout_info(const glp_witness_layout* layout, uint32_t* log_n, uint32_t* n_wires, uint64_t* n_src, uint32_t* n_pos_rows,
+                            uint32_t* n_sha_rows, uint32_t* n_public);
+/* B wire matrices from B rows of an evaluated slab (d_values [rows][value_stride] as glp_witness_eval_device leaves it, the fixed values behind
+ * the variables of each row; value_stride >= n_src).  Instance i reads slab row h_rows[i] (host, [B]; any order, repeats allowed) and its matrix
+ * is written at d_wires + i * wire_stride_words (wire_stride_words >= n_wires * n; words past n_wires * n are left alone): B matrices side by
+ * side, the layout glp_plonk_prove_batch's pointers name.  The derived wires of the Poseidon and SHA rows are filled as
+ * glp_poseidon_gate_fill_rows / glp_sha_gate_fill_rows fill them (same kernel bodies, same small-MDS choice): every word equals what
+ * glp_gather_u64 and the two row fillers give per instance.  h_public ([B][n_public], or NULL): the public values of each instance.
+ * Whatever B is, the call issues
+ *   launches     = 1 (all B matrices: one work-item per cell, a loop over the instances) + (Poseidon rows ? 1 : 0) + (SHA rows ? 1 : 0)
+ *                  + (h_public && n_public ? 1 : 0)                                                   <= 4
+ *   synchronises = (h_public && n_public ? 1 : 0), after the one device-to-host copy                     <= 1
+ * and one host-to-device copy of the B slab rows (from pinned staging of the ctx: h_rows is done with on return; before it is overwritten the
+ * next call waits for the event behind the previous call's copy).  Without h_public the call is stream-ordered and returns at once.
+ * glp_witness_last_place_counts reports the two numbers of the LAST call on the ctx.
+ * Measured (profiles/reduce_batch.json; 8 data-commitment leaves of 2^16 x 144, resident slab -> resident wires + public values, medians of 5
+ * alternating repeats): eight glp_gather_u64 / row filler / public gather sequences 1.83 ms, one call here 0.63 ms.
+ * B == 0 is GLP_OK and does nothing.  GLP_E_INVALID for a null argument or a stride below the layout's; GLP_E_STATE when the layout has Poseidon
+ * rows and the ctx has no Poseidon constants; GLP_E_UNSUPPORTED for a B whose row launches would exceed 2^31 - 1 workgroups.
+ * THE CALLER'S CONTRACT, which the callee cannot check: every h_rows[i] is a row of the slab (< its row count), as value_stride is the caller's
+ * for glp_witness_eval_device; and the B destination matrices do not overlap the slab or each other. */
+int glp_witness_place_batch(glp_ctx* ctx, const glp_witness_layout* layout, const uint64_t* d_values, size_t value_stride, const uint32_t* h_rows,
+                            uint32_t B, uint64_t* d_wires, size_t wire_stride_words, uint64_t* h_public);
+int glp_witness_last_place_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
 /* the Poseidon permutation on the host: n states of 12 canonical words, in place (same constants arguments as the host verifiers) */
 int glp_poseidon_permute_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, uint64_t* states, size_t n);
 int glp_plonk_proof_digest_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* h_proof,
