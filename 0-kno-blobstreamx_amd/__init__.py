@@ -57,6 +57,55 @@ class CircuitShape(ctypes.Structure):
                 ("rate_bits", ctypes.c_uint32), ("cap_height", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class CheckViolation(ctypes.Structure):
+    """glp_check_violation"""
+    _fields_ = [("kind", ctypes.c_uint32), ("row", ctypes.c_uint32), ("index", ctypes.c_uint32), ("n_in_row", ctypes.c_uint32),
+                ("peer_wire", ctypes.c_uint32), ("peer_row", ctypes.c_uint32), ("value", ctypes.c_uint64), ("peer_value", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class CheckSummary(ctypes.Structure):
+    """glp_check_summary"""
+    _fields_ = [("n_gate_bad", ctypes.c_uint64), ("n_copy_bad", ctypes.c_uint64), ("n_gate_rows", ctypes.c_uint32),
+                ("n_copy_rows", ctypes.c_uint32), ("n_listed", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+CHECK_GATE, CHECK_COPY = 0, 1
+CHECK_KIND_NAMES = {CHECK_GATE: "gate", CHECK_COPY: "copy"}
+
+
+class CheckResult:
+    """what PlonkCircuit.check* found for one witness: ok, summary (dict of the glp_check_summary counts) and violations (list of dicts, one per
+    failing row and kind with that row's lowest failing index, ascending by (row, kind), at most max_list of them)"""
+
+    def __init__(self, ok, summary, violations):
+        self.ok, self.summary, self.violations = bool(ok), summary, violations
+
+    def __bool__(self):
+        return self.ok
+
+    def first(self):
+        return self.violations[0] if self.violations else None
+
+    def describe(self):
+        if self.ok:
+            return "satisfied"
+        s = self.summary
+        head = f"{s['n_gate_bad']} failing gate constraints in {s['n_gate_rows']} rows, {s['n_copy_bad']} copy mismatches in {s['n_copy_rows']} rows"
+        v = self.first()
+        if v is None:
+            return head
+        return f"row {v['row']}, kind {CHECK_KIND_NAMES[v['kind']]}, index {v['index']} ({head})"
+
+    def __repr__(self):
+        return f"CheckResult({self.describe()})"
+
+
 PLONK_NCONST = 6                 # constant columns: q_arith, c0, c1, c2, q_pi, q_pos
 PLONK_NCONST_SHA = 10            # ... + q_she, q_sha, q_shw, q_add for circuits with SHA-256 rows
 CIRCUIT_SHA_GATES = 2
@@ -206,6 +255,9 @@ def load_library():
         "glp_plonk_prove_batch": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t)]),
         "glp_plonk_last_batch_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
+        "glp_plonk_check_witness": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32]),
+        "glp_plonk_check_witness_batch": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32]),
+        "glp_plonk_last_check_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "glp_plonk_verify_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_uint32,
                                                ctypes.c_uint32]),
         "glp_plonk_verify_host_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
@@ -856,6 +908,12 @@ class Prover:
         self._chk(self.lib.glp_plonk_last_batch_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_plonk_last_batch_counts")
         return tuple(x.value for x in v)
 
+    def plonk_last_check_counts(self):
+        """(kernel launches, stream synchronises) of the last PlonkCircuit.check* on this prover (glp_plonk_last_check_counts)"""
+        a, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._chk(self.lib.glp_plonk_last_check_counts(self.ctx, ctypes.byref(a), ctypes.byref(b)), "glp_plonk_last_check_counts")
+        return a.value, b.value
+
     def pow_grind_batch(self, seeds, pow_bits):
         """seeds [B][4] -> B nonces, each what pow_grind returns for that seed"""
         sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1, 4)
@@ -1161,6 +1219,55 @@ class PlonkCircuit:
         finally:
             for b in bufs:
                 b.free()
+
+    # ---- witness checker (glp_plonk_check_witness[_batch]): never raises for a bad witness, only for unusable arguments or a bad key ----
+    def check_batch_(self, d_wires_list, publics=None, max_list=16):
+        """B device wire matrices of this circuit against its constraints in one call.  Returns B CheckResults (ok, summary, violations)."""
+        B = len(d_wires_list)
+        if B == 0:
+            return []
+        if publics is None:
+            publics = [None] * B
+        if len(publics) != B:
+            raise GlpError(f"{len(publics)} public-input lists given for {B} instances")
+        rows = [self._public_words(p) for p in publics]
+        pub = np.ascontiguousarray(np.stack(rows), dtype=np.uint64) if self.n_public else None
+        ptrs = (_vp * B)(*[_ptr(d) for d in d_wires_list])
+        status = (ctypes.c_int32 * B)()
+        sums = (CheckSummary * B)()
+        lists = (CheckViolation * max(B * max_list, 1))()
+        self.prover._chk(self.prover.lib.glp_plonk_check_witness_batch(self.prover.ctx, self.h, ptrs, pub.ctypes.data if pub is not None else None, B,
+                                                                       status, sums, lists if max_list else None, max_list),
+                         "glp_plonk_check_witness_batch")
+        return [CheckResult(status[b] == 0, sums[b].as_dict(), [lists[b * max_list + k].as_dict() for k in range(sums[b].n_listed)]) for b in range(B)]
+
+    def require_satisfied_(self, d_wires_list, publics=None, names=None):
+        """check_batch_ for callers that must not prove a bad witness (the check_witness=True paths of the MapReduce classes): ValueError naming
+        the first failing instance (names[i], default 'instance i'), its row, the kind and the index"""
+        for i, res in enumerate(self.check_batch_(d_wires_list, publics, max_list=1)):
+            if not res.ok:
+                raise ValueError(f"check_witness: {names[i] if names else f'instance {i}'}: witness not satisfied: {res.describe()}")
+
+    def check_(self, d_wires, public=None, max_list=16):
+        """one device wire matrix (glp_plonk_check_witness) -> CheckResult"""
+        pub = self._public_words(public)
+        sm = CheckSummary()
+        lst = (CheckViolation * max(max_list, 1))()
+        rc = self.prover.lib.glp_plonk_check_witness(self.prover.ctx, self.h, _ptr(d_wires), pub.ctypes.data if pub is not None else None,
+                                                     ctypes.byref(sm), lst if max_list else None, max_list)
+        if rc not in (0, -7):
+            self.prover._chk(rc, "glp_plonk_check_witness")
+        return CheckResult(rc == 0, sm.as_dict(), [lst[k].as_dict() for k in range(sm.n_listed)])
+
+    def check(self, wires, public=None, max_list=16):
+        """check_ for a host array [n_wires][n]"""
+        w = np.ascontiguousarray(wires, dtype=np.uint64)
+        assert w.shape == (self.n_wires, 1 << self.log_n)
+        dw = self.prover.to_device(w)
+        try:
+            return self.check_(dw, public, max_list)
+        finally:
+            dw.free()
 
     def debug_stage(self, wires, which, challenges, public=None):
         """parity hook (glp_plonk_debug_stage): which = "zs" -> [2*M][n] Z / partial products on the trace domain for

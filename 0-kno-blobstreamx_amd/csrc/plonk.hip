@@ -14,6 +14,7 @@
 #include <memory>
 #include <vector>
 #include "glp_ctx.h"
+#include "plonk_circuit.h"
 #include "hash_state.h"
 #include "challenger.h"
 #include "plonk_kernels.cuh"
@@ -28,23 +29,8 @@ uint8_t* glp_words_to_blob(const std::vector<u64>& P, size_t* len);
 
 namespace {
 typedef GlpPoolBuf DBuf;     // ctx pool blocks (glp_ctx.h)
-struct Commit {                 // one PolynomialBatch kept on the device
-    DBuf coeffs, lde, dig;
-    std::vector<u64> cap;
-    u32 n_polys = 0;
-    explicit Commit(glp_ctx* c) : coeffs(c), lde(c), dig(c) {}
-};
+typedef GlpCommit Commit;    // one PolynomialBatch kept on the device; struct glp_plonk_circuit: plonk_circuit.h
 }  // namespace
-
-struct glp_plonk_circuit {       // must be freed (glp_plonk_free) before its ctx is destroyed
-    u32 log_n, W, R, n_public, flags, rate_bits, cap_h;
-    u64 shift;
-    DBuf sigma_vals;            // [R][n] values on the trace domain (K6 input)
-    DBuf ks, inv_xm1;
-    std::vector<u64> h_ks;
-    Commit pre;                 // constants + sigmas
-    explicit glp_plonk_circuit(glp_ctx* c) : sigma_vals(c), ks(c), inv_xm1(c), pre(c) {}
-};
 
 // values [n_polys][n] (device, consumed: turned into coefficients in place) -> Commit
 static int commit_values(glp_ctx* c, u64* d_vals_owned, u32 n_polys, u32 log_n, u32 rb, u32 cap_h, Commit& out) {

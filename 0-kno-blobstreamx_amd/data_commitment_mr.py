@@ -100,7 +100,7 @@ class DataCommitmentMapReduce:
         return 80
 
     def __init__(self, prover, poseidon_consts, leaf_blocks=64, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
-                 device_witness_chunk=32, prove_batch=0):
+                 device_witness_chunk=32, prove_batch=0, check_witness=False):
         """map_provers: further Provers on the same GPU (their Poseidon constants set): the Map step then proves leaves on all of them at once,
         one host thread each (the latency-bound phases of one leaf proof overlap the throughput-bound phases of another, as in mapreduce.py).
         device_witness (default off: the host evaluator pool): the Map step evaluates the leaves' witness programs ON THE DEVICE, device_witness_chunk
@@ -119,7 +119,11 @@ class DataCommitmentMapReduce:
         whole level to one prover): it is opt-in, for hosts that drive one prover per GPU.
         Memory: a group of k nodes of 2^17 x 144 holds k * 151 MB of wires.
         The batched prover holds k * 1.2 GB of wire LDE per prover on top of that (GLP_E_UNSUPPORTED from glp_plonk_prove_batch is the only hard
-        limit)."""
+        limit).
+        check_witness (default off): every leaf witness and every node witness goes through the witness checker (PlonkCircuit.check_batch_: the
+        gate constraints on the trace rows and the copy constraints cell by cell) after placement and before it is proved — a group of
+        a batched call in ONE checker call.  A failing witness raises ValueError naming the leaf or node, the row, the kind and the index; the
+        proofs of satisfied witnesses are byte for byte those of the unchecked path."""
         assert leaf_blocks >= 1 and leaf_blocks & (leaf_blocks - 1) == 0 and fan_in >= 2 and fan_in & (fan_in - 1) == 0
         self.prover, self.consts = prover, tuple(np.ascontiguousarray(a, dtype=np.uint64) for a in poseidon_consts)
         self.map_provers, self.map_circuits = list(map_provers), []
@@ -130,8 +134,20 @@ class DataCommitmentMapReduce:
         self.record_seconds = {}
         self.device_witness, self.device_witness_chunk = bool(device_witness), max(1, int(device_witness_chunk))
         self.prove_batch, self._batch_bufs = max(0, int(prove_batch)), {}
+        self.check_witness = bool(check_witness)
+        self._placed_hook = None        # tests: called as hook(prover, address of a placed wire matrix, leaf number) before the check
 
-    def _prove_group(self, prover, circuit, place, count, place_all=None):
+    def _check_placed(self, circuit, addrs, publics, names):
+        """the check_witness step for wire matrices that are placed and about to be proved (no-op unless check_witness)"""
+        if not getattr(self, "check_witness", False):
+            return
+        hook = getattr(self, "_placed_hook", None)
+        if hook is not None:
+            for a, nm in zip(addrs, names):
+                hook(circuit.prover, getattr(a, "ptr", a), nm)
+        circuit.require_satisfied_(addrs, publics, [f"leaf {nm}" for nm in names])
+
+    def _prove_group(self, prover, circuit, place, count, place_all=None, names=None):
         """one prove_batch_ call for `count` <= prove_batch leaves: place(j, address) lays leaf j's wire matrix at that address of this prover's
         [k][W][n] buffer and returns its public values — or place_all(address) lays all `count` matrices side by side from there in one call and
         returns the list of their public values; returns the proofs in order"""
@@ -141,6 +157,7 @@ class DataCommitmentMapReduce:
             buf = self._batch_bufs[id(prover)] = DeviceBuffer(prover, self.prove_batch * words * 8)
         addrs = [buf.ptr + j * words * 8 for j in range(count)]
         publics = place_all(buf.ptr) if place_all is not None else [place(j, addrs[j]) for j in range(count)]
+        self._check_placed(circuit, addrs, publics, list(names) if names is not None else list(range(count)))
         return circuit.prove_batch_(addrs, publics, self.nq, self.pw)
 
     # ---- Map ----------------------------------------------------------------------------------------------------------------------
@@ -172,6 +189,7 @@ class DataCommitmentMapReduce:
         inputs = [w for h, r in zip(heights, data_roots) for w in tuple_words(h, r)]
         vals = self.leaf_program.evaluate(self.consts, inputs, threads=1)
         dw, public = self.leaf_program.device_witness(prover, vals, reuse=True)          # the program's own buffer: no allocation per leaf
+        self._check_placed(circuit, [dw], [public], [0])
         return circuit.prove_(dw, self.nq, self.pw, public=public), public
 
     def _map_inputs(self, inputs_list):
@@ -199,10 +217,11 @@ class DataCommitmentMapReduce:
                     for g in range(0, len(share), self.prove_batch):
                         ids = share[g:g + self.prove_batch]
                         place = lambda j, addr, ids=ids: self.leaf_program.device_witness(prover, futs[ids[j]].result(), out=addr)[1]
-                        out += zip(ids, self._prove_group(prover, circuit, place, len(ids)))
+                        out += zip(ids, self._prove_group(prover, circuit, place, len(ids), names=ids))
                     return out
                 for i in share:
                     dw, public = self.leaf_program.device_witness(prover, futs[i].result(), reuse=True)
+                    self._check_placed(circuit, [dw], [public], [i])
                     out.append((i, circuit.prove_(dw, self.nq, self.pw, public=public)))
                 return out
             try:
@@ -247,11 +266,12 @@ class DataCommitmentMapReduce:
                         for g in range(0, len(share), self.prove_batch):
                             ids = share[g:g + self.prove_batch]
                             place_all = lambda addr, ids=ids: slab.device_witness_batch(prover, ids, addr)
-                            for i, proof in zip(ids, self._prove_group(prover, circuit, None, len(ids), place_all=place_all)):
+                            for i, proof in zip(ids, self._prove_group(prover, circuit, None, len(ids), place_all=place_all, names=[lo + i for i in ids])):
                                 out[lo + i] = proof
                         return
                     for i in share:
                         dw, public = slab.device_witness(prover, i, reuse=True)
+                        self._check_placed(circuit, [dw], [public], [lo + i])
                         out[lo + i] = circuit.prove_(dw, self.nq, self.pw, public=public)
                 if pool is None:
                     work(0)
@@ -300,12 +320,13 @@ class DataCommitmentMapReduce:
                 raise ValueError("the number of proofs at a level is not a multiple of a power-of-two fan-in")
             t0 = time.perf_counter()
             rp = self._node(level, cur[:fan], key, span)
+            cw = getattr(self, "check_witness", False)
             groups = [cur[k:k + fan] for k in range(0, len(cur), fan)]
             if getattr(self, "device_witness", False):
-                done = self._reduce_level_device(rp, groups)
+                done = self._reduce_level_device(rp, groups, level)
                 nxt, public = [d[0] for d in done], done[-1][1]
             elif len(groups) > 1 and getattr(self, "prove_batch", 0):
-                done = self._reduce_level_batched(rp, groups)
+                done = self._reduce_level_batched(rp, groups, level)
                 nxt, public = [d[0] for d in done], done[-1][1]
             elif len(groups) > 1 and self.map_provers:
                 # several nodes of one level: one host thread per prover, each with its own commitment of the level's (shared) recording
@@ -317,14 +338,14 @@ class DataCommitmentMapReduce:
                 def work(w):
                     if w:
                         self.map_provers[w - 1].bind_thread()
-                    return [(g, workers[w].prove(groups[g], self.nq, self.pw)) for g in range(w, len(groups), len(workers))]
+                    return [(g, workers[w].prove(groups[g], self.nq, self.pw, check_witness=cw, name=f"level {level} node {g}")) for g in range(w, len(groups), len(workers))]
                 with ThreadPoolExecutor(len(workers)) as ex:
                     done = sorted((r for f in [ex.submit(work, w) for w in range(len(workers))] for r in f.result()), key=lambda t: t[0])
                 nxt, public = [pr_[0] for _, pr_ in done], done[-1][1][1]
             else:
                 nxt = []
-                for grp in groups:
-                    proof, public = rp.prove(grp, self.nq, self.pw)
+                for g, grp in enumerate(groups):
+                    proof, public = rp.prove(grp, self.nq, self.pw, check_witness=cw, name=f"level {level} node {g}")
                     nxt.append(proof)
             if timings is not None:
                 timings.append({"level": level, "nodes": len(nxt), "fan_in": fan, "rows": rp.stats["rows"],
@@ -348,10 +369,11 @@ class DataCommitmentMapReduce:
             workers += self.node_replicas[id(rp)]
         return workers
 
-    def _reduce_level_batched(self, rp, groups):
+    def _reduce_level_batched(self, rp, groups, level=0):
         """the nodes of one level (at least two) with prove_batch = k > 0 and host witnesses: contiguous runs of up to k nodes, run j on worker
         j mod (number of workers), each run ONE RecursionProgram.prove_batch call into that worker's group buffer.  [(proof, public)] in order.
-        A refused child raises prove's text with the node's position in the level ('instance i: ...') and nothing is returned."""
+        A refused child raises prove's text with the node's position in the level ('instance i: ...') and nothing is returned; with check_witness a
+        node witness that fails the checker raises 'check_witness: level L node g: ...', g the node's position in the level."""
         from concurrent.futures import ThreadPoolExecutor
         workers = self._level_workers(rp, groups)
         k = self.prove_batch
@@ -363,8 +385,11 @@ class DataCommitmentMapReduce:
                 self.map_provers[w - 1].bind_thread()
             for lo, run in runs[w::len(workers)]:
                 try:
-                    done = workers[w].prove_batch(run, self.nq, self.pw)
+                    done = workers[w].prove_batch(run, self.nq, self.pw, check_witness=getattr(self, "check_witness", False),
+                                                  names=[f"level {level} node {lo + i}" for i in range(len(run))])
                 except ValueError as e:
+                    if str(e).startswith("check_witness: "):        # names the node's position in the level already
+                        raise
                     raise ValueError(_rebase_instance(str(e), lo, len(run) == 1)) from None
                 out[lo:lo + len(run)] = done
         n_active = min(len(workers), len(runs))
@@ -387,7 +412,7 @@ class DataCommitmentMapReduce:
                     raise err
         return out
 
-    def _reduce_level_device(self, rp, groups):
+    def _reduce_level_device(self, rp, groups, level=0):
         """the nodes of one level with their witnesses made on the device: device_witness_chunk groups at a time through rp.witness_batch on the
         main prover (which returns with its stream synchronised), then every prover — the main one and, for several groups, rp's replicas on the
         map provers — places and proves its share of the chunk from the slab, as _map_inputs_device does for leaves.  [(proof, public)] in order.
@@ -396,6 +421,7 @@ class DataCommitmentMapReduce:
         from concurrent.futures import ThreadPoolExecutor
         workers = self._level_workers(rp, groups)
         batch = getattr(self, "prove_batch", 0) if len(groups) > 1 else 0
+        cw = getattr(self, "check_witness", False)
         n_workers, chunk = len(workers), self.device_witness_chunk
         out = [None] * len(groups)
         pool = ThreadPoolExecutor(n_workers - 1) if n_workers > 1 else None
@@ -417,10 +443,13 @@ class DataCommitmentMapReduce:
                     if batch:
                         runs = [range(r, min(r + batch, len(part))) for r in range(0, len(part), batch)]
                         for run in runs[w::n_workers]:
-                            out[lo + run[0]:lo + run[0] + len(run)] = workers[w].prove_placed(slab, run, self.nq, self.pw)
+                            out[lo + run[0]:lo + run[0] + len(run)] = workers[w].prove_placed(slab, run, self.nq, self.pw, check_witness=cw,
+                                                                                              names=[f"level {level} node {lo + i}" for i in run])
                         return
                     for i in range(w, len(part), n_workers):
                         dw, public = slab.device_witness(workers[w].prover, i, reuse=True)
+                        if cw:
+                            workers[w].circuit.require_satisfied_([dw], [public], [f"level {level} node {lo + i}"])
                         out[lo + i] = (workers[w].circuit.prove_(dw, self.nq, self.pw, public=public), public)
                 if pool is None:
                     work(0)
@@ -615,13 +644,14 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
 
     def __init__(self, prover, poseidon_consts, leaf_headers=8, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), height_varint_bytes=4,
                  field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), defer_commitment=None, device_witness=False,
-                 device_witness_chunk=32, prove_batch=0):
+                 device_witness_chunk=32, prove_batch=0, check_witness=False):
         """defer_commitment (default: leaves of 8 or more headers): the leaves expose their headers' data hashes and the LEVEL-1 NODES hash the
         (height, data_hash) tuples and the leaf subtrees — round 3: an 8-header leaf is 368 compressions x 178 rows = 2.7k rows past 2^16; without
         its 30 tuple / subtree compressions it fits 2^16 rows (half the leaf proof), and the node circuit (75k of 131k rows used) has the room.
         The statement of every node — hence of the root — is unchanged; a chain of ONE leaf has no node and is refused in this mode."""
         super().__init__(prover, poseidon_consts, leaf_blocks=leaf_headers, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
-                         map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch)
+                         map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch,
+                         check_witness=check_witness)
         self.defer = (leaf_headers >= 8) if defer_commitment is None else bool(defer_commitment)
         if self.defer and leaf_headers & (leaf_headers - 1):
             raise ValueError("deferred tuple hashing needs a power-of-two number of headers per leaf")
@@ -691,6 +721,7 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
         prover, circuit = (self.prover, self.leaf_circuit) if which == 0 else (self.map_provers[which - 1], self.map_circuits[which - 1])
         vals = self.leaf_program.evaluate(self.consts, _chain_leaf_inputs(start_hash, first_height, headers, self.n_groups), threads=1)
         dw, public = self.leaf_program.device_witness(prover, vals, reuse=True)
+        self._check_placed(circuit, [dw], [public], [0])
         return circuit.prove_(dw, self.nq, self.pw, public=public), public
 
     @staticmethod

@@ -49,11 +49,11 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
     vote_format = None                              # a blobstream.VoteFormat in CanonicalVoteSetMapReduce
 
     def __init__(self, prover, poseidon_consts, msg_len=112, hash_offset=16, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
-                 device_witness_chunk=32, prove_batch=0):
+                 device_witness_chunk=32, prove_batch=0, **kw):
         if hash_offset + 32 > msg_len or hash_offset % 4 or msg_len % 4:
             raise ValueError("the vote bytes must hold a 32-byte block hash at a word-aligned offset")
         super().__init__(prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits, map_provers=map_provers,
-                         device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch)
+                         device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch, **kw)     # kw: check_witness
         self.msg_len, self.hash_offset = int(msg_len), int(hash_offset)
 
     def _child_n_public(self, level):
@@ -122,6 +122,7 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         inputs = witness_inputs(pubkey, signature if flag else bytes(64), msg, bool(flag), vote_format=self.vote_format)
         vals = self.leaf_program.evaluate(self.consts, inputs, threads=1)
         dw, public = self.leaf_program.device_witness(prover, vals, reuse=True)
+        self._check_placed(circuit, [dw], [public], [0])
         return circuit.prove_(dw, self.nq, self.pw, public=public), public
 
     def _slots(self, pubkeys, signatures, msgs, flags, total=None):
@@ -267,10 +268,10 @@ class CanonicalVoteSetMapReduce(SignatureSetMapReduce):
     _NANOS = (0, 5, 300, 70_000, 3_000_000, 999_999_999)                      # varints of 0 (field omitted), 1, 2, 3, 4 and 5 bytes
 
     def __init__(self, prover, poseidon_consts, vote_format, chain_id="celestia", round=0, part_total=1, part_hash=bytes(32), seconds=1_700_000_000,
-                 fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False, device_witness_chunk=32, prove_batch=0):
+                 fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False, device_witness_chunk=32, prove_batch=0, **kw):
         DataCommitmentMapReduce.__init__(self, prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
                                          map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk,
-                                         prove_batch=prove_batch)
+                                         prove_batch=prove_batch, **kw)                                                 # kw: check_witness
         if bool(round) != vote_format.round_present:
             raise ValueError("the vote format and the round disagree about the round field")
         self.vote_format = vote_format

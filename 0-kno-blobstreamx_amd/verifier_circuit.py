@@ -784,13 +784,16 @@ class RecursionProgram:
         self.program.check_words_device(slab, words)
         return slab
 
-    def prove(self, proofs, num_queries=28, pow_bits=16, device_witness=False):
+    def prove(self, proofs, num_queries=28, pow_bits=16, device_witness=False, check_witness=False, name="node"):
         """(root proof, public inputs) for a batch of proofs of the leaf circuit.  device_witness: the witness through witness_batch (evaluated
-        and checked on the device) instead of the host evaluator: the same proof."""
+        and checked on the device) instead of the host evaluator: the same proof.  check_witness: the placed wire matrix goes through the
+        witness checker (PlonkCircuit.require_satisfied_) before it is proved; ValueError naming `name`, the row, the kind and the index."""
         if device_witness:
             dw, public = self.witness_batch([proofs]).device_witness(self.prover, 0, reuse=True)
         else:
             dw, public = self.witness(proofs, reuse=True)
+        if check_witness:
+            self.circuit.require_satisfied_([dw], [public], [name])
         return self.circuit.prove_(dw, num_queries, pow_bits, public=public), public
 
     def _group_buffer(self, count):
@@ -809,7 +812,7 @@ class RecursionProgram:
         if buf is not None and buf.ptr is not None and getattr(buf.prover, "ctx", None):
             buf.free()
 
-    def prove_placed(self, slab, ids, num_queries=28, pow_bits=16):
+    def prove_placed(self, slab, ids, num_queries=28, pow_bits=16, check_witness=False, names=None):
         """[(proof, public)] for the rows `ids` of an evaluated and checked slab (witness_batch of this program, made on this prover or on another
         ctx of the same device): ONE placement call (DeviceWitnessBatch.device_witness_batch) into this object's group buffer, then ONE
         PlonkCircuit.prove_batch_ — each proof byte for byte what prove gives for that group alone."""
@@ -819,10 +822,13 @@ class RecursionProgram:
         words = self.program.W << self.program.log_n
         buf = self._group_buffer(len(ids))
         publics = slab.device_witness_batch(self.prover, ids, buf)
-        proofs = self.circuit.prove_batch_([buf.ptr + j * words * 8 for j in range(len(ids))], publics, num_queries, pow_bits)
+        addrs = [buf.ptr + j * words * 8 for j in range(len(ids))]
+        if check_witness:
+            self.circuit.require_satisfied_(addrs, publics, names or [f"node {i}" for i in ids])
+        proofs = self.circuit.prove_batch_(addrs, publics, num_queries, pow_bits)
         return list(zip(proofs, publics))
 
-    def prove_batch(self, groups, num_queries=28, pow_bits=16, device_witness=False):
+    def prove_batch(self, groups, num_queries=28, pow_bits=16, device_witness=False, check_witness=False, names=None):
         """prove for SEVERAL batches of proofs (the nodes of a Reduce level) with ONE prover call: [(proof, public)] in order, each what
         prove(group) returns, byte for byte.  device_witness: witness_batch(groups), then prove_placed.  Otherwise the host evaluator and
         check_words per group as in witness(), each matrix placed into its slot of the group buffer (WitnessProgram.device_witness(out=)), then
@@ -835,7 +841,7 @@ class RecursionProgram:
         if not groups:
             return []
         if device_witness:
-            return self.prove_placed(self.witness_batch(groups), range(len(groups)), num_queries, pow_bits)
+            return self.prove_placed(self.witness_batch(groups), range(len(groups)), num_queries, pow_bits, check_witness=check_witness, names=names)
         words = self.program.W << self.program.log_n
         buf = self._group_buffer(len(groups))
         addrs = [buf.ptr + j * words * 8 for j in range(len(groups))]
@@ -848,6 +854,8 @@ class RecursionProgram:
             except ValueError as e:
                 raise ValueError((f"instance {i}: " if len(groups) > 1 else "") + str(e)) from None
             publics.append(self.program.device_witness(self.prover, vals, out=addrs[i])[1])
+        if check_witness:                # every group after placement, before anything is proved: one checker call for the level's groups
+            self.circuit.require_satisfied_(addrs, publics, names or [f"node {i}" for i in range(len(groups))])
         return list(zip(self.circuit.prove_batch_(addrs, publics, num_queries, pow_bits), publics))
 
     def free(self):

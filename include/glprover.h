@@ -344,6 +344,53 @@ int glp_sha_gate_fill_rows(glp_ctx* ctx, uint64_t* d_wire_vals, uint32_t log_n, 
 int glp_plonk_debug_stage(glp_ctx* ctx, glp_plonk_circuit* ck, const uint64_t* d_wire_vals, const uint64_t* h_public, int which,
                           const uint64_t* h_challenges, uint64_t* d_out);
 
+/* ---- witness checker: does a wire matrix satisfy the circuit the key commits to, and if not, where (opt-in; the prover never calls it) ----
+ * Evaluated on every row i of the trace domain, natural order, with the KEY's constants and sigmas (the constant columns come back from the
+ * preprocessed commitment's coefficients by one forward NTT into a transient buffer; nothing is taken from the caller):
+ *   GLP_CHECK_GATE  index = the constraint's number in the quotient's alpha order: 1 the public input  q_pi * wire_0 - PI(i)  (PI(i) =
+ *                   h_public[i] for i < n_public, else 0); 3+3c, 4+3c the two arithmetic / extension slots of chunk c (q_arith * gate +
+ *                   q_ext * e); 2+3M+k Poseidon constraint k times q_pos (M = n_routed / 8; the small-integer-MDS body when the ctx's MDS is
+ *                   small, as the prover's quotient kernel chooses); then the 140 selector-weighted SHA slots
+ *   GLP_CHECK_COPY  index = routed wire j: cell (j, row) differs from the cell sigma sends it to — the copy constraints tested directly
+ * Not evaluated: L_1 (Z - 1) (index 0) and the permutation-chunk constraints (index 2+3c) need Z; the direct copy check stands in their place.
+ * sum: the counts.  list (may be NULL when max_list == 0): one entry per failing row and kind, carrying that row's LOWEST failing index,
+ * ascending by (row, kind), at most max_list entries (n_listed of them written); the same input always gives the same list.
+ * Single form: GLP_OK when every constraint holds, GLP_E_REJECT when not (sum, list and glp_last_error name the first violation).
+ * Batch form: B witnesses of one key in the same launches; GLP_OK when it ran, the verdict of instance b in h_status[b] (GLP_OK / GLP_E_REJECT),
+ * sums[b], lists[b * max_list ..].  Argument rules as glp_plonk_prove_batch: B == 0 is GLP_OK and does nothing, two instances may point at the
+ * same matrix, GLP_E_INVALID for a null argument or a non-canonical public input (glp_last_error names the instance), GLP_E_UNSUPPORTED for
+ * B > 65535 (the instance is a grid dimension), GLP_E_STATE for a Poseidon circuit on a ctx without constants.
+ * The key's FIRST check decodes its sigma values (k_j' * w_n^i', with the ctx's roots of unity) into cell indices, one u32 per routed cell:
+ * 4 * n_routed * n bytes, kept on the key and freed with it; a key that is never checked holds nothing more than before.  GLP_E_INVALID, with
+ * the cell named in glp_last_error, when a sigma value is no routed cell of the domain or sigma is no permutation of the routed cells.
+ * Whatever B is (glp_plonk_last_check_counts): launches = [first check of a key: 2] + 1 (the NTT call) + 1 (base) + (Poseidon rows ? 1 : 0) +
+ * (SHA rows ? 1 : 0) + 1 (copy); synchronises = 1 — the device builds the lists, counts and lists come back with that one synchronise.
+ * The count is of the driver's explicit stream synchronises; the device-to-host copies of the counters and lists land in pageable host
+ * memory, where the runtime may wait for each copy as it is issued.
+ * d_wire_vals must hold canonical words (< p), as for the prover: cells are compared as 64-bit words, so a non-canonical representative
+ * of the value its peer holds is reported as a copy mismatch.
+ * Cost of a FAILING witness: the list is written by one 256-lane workgroup per instance, which walks the rows from the first failing one in
+ * steps of 256 until max_list entries are found or the rows end — at most n / 256 steps (256 at n = 2^16, 65536 at n = 2^24) when fewer than
+ * max_list (row, kind) pairs fail; a satisfied witness takes none.  Pass the max_list you will read, not a large one.
+ * Transient device memory: 8 * n_const * n + B * (44 * n + 40 * max_list) bytes (+ 4 * n_routed * n during the decode). */
+#define GLP_CHECK_GATE 0u
+#define GLP_CHECK_COPY 1u
+typedef struct {
+    uint32_t kind, row, index, n_in_row;      /* n_in_row: failing constraints (GATE) or wires (COPY) in this row */
+    uint32_t peer_wire, peer_row;             /* COPY: the cell sigma names; GATE: 0 */
+    uint64_t value, peer_value;               /* GATE: value = the term the quotient weights by alpha^index, on this trace row; COPY: the two cell values */
+} glp_check_violation;
+typedef struct {
+    uint64_t n_gate_bad, n_copy_bad;          /* failing (row, constraint) and (row, wire) pairs */
+    uint32_t n_gate_rows, n_copy_rows, n_listed;
+} glp_check_summary;
+int glp_plonk_check_witness(glp_ctx* ctx, glp_plonk_circuit* ck, const uint64_t* d_wire_vals, const uint64_t* h_public, glp_check_summary* sum,
+                            glp_check_violation* list, uint32_t max_list);
+int glp_plonk_check_witness_batch(glp_ctx* ctx, glp_plonk_circuit* ck, const uint64_t* const* d_wire_vals, const uint64_t* h_public, uint32_t B,
+                                  int32_t* h_status, glp_check_summary* sums, glp_check_violation* lists, uint32_t max_list);
+/* what the LAST glp_plonk_check_witness[_batch] on this ctx issued: kernel launches (the NTT call counts as one) and stream synchronises */
+int glp_plonk_last_check_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
+
 /* the circuit's preprocessed commitment (cap of the constants + sigmas batch) = its verifying key:
  * copies min(*n_words, needed) u64 to h_cap and stores the needed count in *n_words */
 int glp_plonk_circuit_cap(glp_plonk_circuit* ck, uint64_t* h_cap, size_t* n_words);
