@@ -75,6 +75,21 @@ class CheckSummary(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class Ed25519InputLayout(ctypes.Structure):
+    """glp_ed25519_input_layout: which form of ed25519_circuit.witness_inputs a row has (ED25519_FORM_*), the window of message lengths
+    (min = max in the plain and the flagged form) and whether the half-size scalar hints follow"""
+    _fields_ = [("form", ctypes.c_uint32), ("msg_len_min", ctypes.c_uint32), ("msg_len_max", ctypes.c_uint32), ("split_scalars", ctypes.c_uint32)]
+
+    def n_words(self):
+        n = ctypes.c_uint64()
+        if load_library().glp_ed25519_leaf_input_words(ctypes.byref(self), ctypes.byref(n)) != 0:
+            raise GlpError("no statement has this input layout")
+        return int(n.value)
+
+
+ED25519_FORM_PLAIN, ED25519_FORM_FLAGGED, ED25519_FORM_VOTE = 0, 1, 2
+ED25519_IN_OK, ED25519_IN_REJECT, ED25519_IN_NO_PAIR, ED25519_IN_INVALID = 0, 1, 2, 3
+
 CHECK_GATE, CHECK_COPY = 0, 1
 CHECK_KIND_NAMES = {CHECK_GATE: "gate", CHECK_COPY: "copy"}
 
@@ -225,6 +240,11 @@ def load_library():
         "glp_sha256_trace": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
         "glp_sha512_trace": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
         "glp_ed25519_witness": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp]),
+        "glp_ed25519_leaf_input_words": (ctypes.c_int, [ctypes.POINTER(Ed25519InputLayout), ctypes.POINTER(ctypes.c_uint64)]),
+        "glp_ed25519_leaf_inputs": (ctypes.c_int, [_vp, ctypes.POINTER(Ed25519InputLayout), _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp,
+                                                   ctypes.c_uint64, _vp, ctypes.c_size_t, _vp]),
+        "glp_ed25519_last_input_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
+        "glp_ed25519_half_scalars": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp]),
         "glp_tm_merkle_root": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp]),
         "glp_challenger_new": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
         "glp_challenger_free": (None, [_vp]),
@@ -1058,6 +1078,72 @@ class Prover:
         for b in (dp, ds, dm, dl, do):
             b.free()
         return out
+
+    def ed25519_leaf_inputs(self, layout, pubs, sigs, msgs, flags=None, dummy=None, out=None):
+        """the input vectors of a signature leaf for B slots, built ON THE DEVICE (glp_ed25519_leaf_inputs): (DeviceBuffer of [B][layout.n_words()]
+        u64, status int32[B] of ED25519_IN_*).  Row i equals ed25519_circuit.witness_inputs of slot i; a row whose status is not OK is zero.
+        pubs / sigs / msgs: lists of bytes (a sig may be None where its flag is 0); flags: one truth value per slot (None in the plain form);
+        dummy: the (pub, sig, msg) triple an unflagged slot verifies (ed25519_circuit.dummy_signature).  out: a DeviceBuffer to reuse."""
+        n, width = len(pubs), layout.n_words()
+        stride = max(1, max((len(m) for m in msgs), default=1))
+        P = np.zeros((n, 32), dtype=np.uint8)
+        S = np.zeros((n, 64), dtype=np.uint8)
+        M = np.zeros((n, stride), dtype=np.uint8)
+        Ln = np.zeros(n, dtype=np.uint32)
+        for i in range(n):
+            P[i] = np.frombuffer(bytes(pubs[i]), dtype=np.uint8)
+            if sigs[i] is not None:
+                S[i] = np.frombuffer(bytes(sigs[i]), dtype=np.uint8)
+            M[i, :len(msgs[i])] = np.frombuffer(bytes(msgs[i]), dtype=np.uint8)
+            Ln[i] = len(msgs[i])
+        parts = [Ln.view(np.uint8), P.reshape(-1), S.reshape(-1), M.reshape(-1)]
+        if layout.form != ED25519_FORM_PLAIN:
+            if flags is None or dummy is None or len(flags) != n:
+                raise GlpError("the flagged forms take one flag per slot and the dummy triple")
+            parts += [np.array([1 if f else 0 for f in flags], dtype=np.uint8), np.frombuffer(b"".join(bytes(x) for x in dummy), dtype=np.uint8)]
+            if parts[-1].size != 96 + layout.msg_len_min:
+                raise GlpError("the dummy triple is pub[32], sig[64] and a message of msg_len_min bytes")
+        # one upload: every array at an 8-byte offset of one block
+        offs, total = [], 0
+        for p in parts:
+            offs.append(total)
+            total += (p.size + 7) & ~7
+        host = np.zeros(max(8, total), dtype=np.uint8)
+        for o, p in zip(offs, parts):
+            host[o:o + p.size] = p
+        need = max(8, n * width * 8)
+        if out is None or out.ptr is None or out.nbytes < need:
+            out = self.alloc(need)
+        status = np.zeros(max(1, n), dtype=np.int32)
+        d = self.to_device(host)
+        at = [d.ptr + o for o in offs] + [None, None]
+        try:
+            self._chk(self.lib.glp_ed25519_leaf_inputs(self.ctx, ctypes.byref(layout), at[1], at[2], at[3], stride, at[0], at[4], at[5], n, out.ptr,
+                                                       width, status.ctypes.data), "glp_ed25519_leaf_inputs")
+        finally:
+            d.free()
+        return out, status[:n]
+
+    def ed25519_last_input_counts(self):
+        """(launches, stream synchronises) of the last ed25519_leaf_inputs on this prover"""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        self._chk(self.lib.glp_ed25519_last_input_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_ed25519_last_input_counts")
+        return tuple(x.value for x in v)
+
+    def ed25519_half_scalars(self, ks):
+        """ed25519_circuit.half_size_pair of each scalar on the device (glp_ed25519_half_scalars): ks = integers below 2^256; returns [n][8] u64
+        = u[3] v[3] neg status (ED25519_IN_OK, _NO_PAIR where the Python raises, _INVALID for k >= L)"""
+        n = len(ks)
+        a = np.array([[(int(k) >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(4)] for k in ks], dtype=np.uint64).reshape(n, 4)
+        if n == 0:
+            return np.zeros((0, 8), dtype=np.uint64)
+        dk, do = self.to_device(a), self.alloc(n * 64)
+        try:
+            self._chk(self.lib.glp_ed25519_half_scalars(self.ctx, dk.ptr, n, do.ptr), "glp_ed25519_half_scalars")
+            return do.download((n, 8))
+        finally:
+            dk.free()
+            do.free()
 
     def tm_merkle_root(self, leaves: bytes, leaf_len: int) -> bytes:
         """Tendermint simple Merkle root of fixed-size leaves (validator set / header fields)"""

@@ -66,6 +66,8 @@ struct glp_ctx {
     uint32_t* place_rows_host = nullptr;
     size_t place_rows_cap = 0;
     hipEvent_t place_ev = nullptr;
+    // what the last glp_ed25519_leaf_inputs issued: kernel launches, stream synchronises (glp_ed25519_last_input_counts)
+    uint32_t ed_input_counts[2] = {0, 0};
 };
 
 // stage timing tree of the prover drivers (the TimingTree of the upstream prover, recalled): a

@@ -411,3 +411,70 @@ extern "C" int glp_ed25519_witness(glp_ctx* c, const uint8_t* d_pubs, const uint
     GLP_HIPCHK(c, hipGetLastError());
     return GLP_OK;
 }
+
+// ---- the signature leaf's input vectors on the device (ed25519_inputs.cuh) --------------------------------------------------------------------
+#include "ed25519_inputs.cuh"
+static_assert(GLP_ED_IN_OK == GLP_ED25519_IN_OK && GLP_ED_IN_REJECT == GLP_ED25519_IN_REJECT && GLP_ED_IN_NO_PAIR == GLP_ED25519_IN_NO_PAIR &&
+              GLP_ED_IN_INVALID == GLP_ED25519_IN_INVALID && GLP_ED_FORM_PLAIN == GLP_ED25519_FORM_PLAIN &&
+              GLP_ED_FORM_FLAGGED == GLP_ED25519_FORM_FLAGGED && GLP_ED_FORM_VOTE == GLP_ED25519_FORM_VOTE && GLP_ED_REC == GLP_ED25519_RECORD_WORDS,
+              "glprover.h and ed25519_inputs.cuh name the same codes");
+
+extern "C" int glp_ed25519_leaf_input_words(const glp_ed25519_input_layout* layout, uint64_t* n_words) {
+    if (!layout || !n_words) return GLP_E_INVALID;
+    const u64 w = glp_ed25519_input_words(layout->form, layout->msg_len_min, layout->msg_len_max, layout->split_scalars);
+    if (!w) return GLP_E_INVALID;
+    *n_words = w;
+    return GLP_OK;
+}
+
+extern "C" int glp_ed25519_leaf_inputs(glp_ctx* c, const glp_ed25519_input_layout* layout, const uint8_t* d_pubs, const uint8_t* d_sigs,
+                                       const uint8_t* d_msgs, uint32_t msg_stride, const uint32_t* d_lens, const uint8_t* d_flags,
+                                       const uint8_t* d_dummy, uint64_t n, uint64_t* d_inputs, size_t input_stride, int32_t* h_status) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->ed_input_counts[0] = c->ed_input_counts[1] = 0;
+    uint64_t width = 0;
+    if (glp_ed25519_leaf_input_words(layout, &width) != GLP_OK) { glp_set_err(c, "glp_ed25519_leaf_inputs: no statement has this layout"); return GLP_E_INVALID; }
+    if (n == 0) return GLP_OK;
+    const bool flagged = layout->form != GLP_ED25519_FORM_PLAIN;
+    if (!d_pubs || !d_sigs || !d_msgs || !d_lens || !d_inputs || !h_status || (flagged && (!d_flags || !d_dummy))) {
+        glp_set_err(c, "glp_ed25519_leaf_inputs: null buffer");
+        return GLP_E_INVALID;
+    }
+    if (msg_stride == 0 || n > (1ull << 30) || input_stride < width) { glp_set_err(c, "glp_ed25519_leaf_inputs: bad size"); return GLP_E_INVALID; }
+    int rc = ensure_sha_tables(c);
+    if (rc) return rc;
+    GlpPoolBuf recs(c), stat(c);
+    if (recs.alloc((size_t)n * GLP_ED_REC * sizeof(u64)) != hipSuccess || stat.alloc((size_t)n * sizeof(int32_t)) != hipSuccess) return GLP_E_HIP;
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    hipLaunchKernelGGL(glp_ed25519_witness_kernel<0>, grid, block, 0, c->stream, d_pubs, d_sigs, d_msgs, msg_stride, d_lens, n, c->hash->d_k512, recs.u());
+    GlpEdInputsArgs a;
+    a.pubs = d_pubs; a.sigs = d_sigs; a.msgs = d_msgs; a.lens = d_lens; a.flags = d_flags; a.dummy = d_dummy; a.recs = recs.u();
+    a.k512 = c->hash->d_k512; a.out = d_inputs; a.status = (int32_t*)stat.p; a.n = n; a.out_stride = input_stride; a.msg_stride = msg_stride;
+    a.form = layout->form; a.lo = layout->msg_len_min; a.hi = layout->msg_len_max; a.split = layout->split_scalars ? 1u : 0u;
+    hipLaunchKernelGGL(glp_ed25519_leaf_inputs_kernel<0>, grid, block, 0, c->stream, a);
+    c->ed_input_counts[0] = 2;
+    GLP_HIPCHK(c, hipGetLastError());
+    GLP_HIPCHK(c, hipMemcpyAsync(h_status, stat.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    c->ed_input_counts[1] = 1;
+    GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+
+extern "C" int glp_ed25519_last_input_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs) {
+    if (!c || !n_launches || !n_host_syncs) return GLP_E_INVALID;
+    *n_launches = c->ed_input_counts[0];
+    *n_host_syncs = c->ed_input_counts[1];
+    return GLP_OK;
+}
+
+extern "C" int glp_ed25519_half_scalars(glp_ctx* c, const uint64_t* d_k, uint64_t n, uint64_t* d_out) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    if ((!d_k || !d_out) && n) { glp_set_err(c, "glp_ed25519_half_scalars: null buffer"); return GLP_E_INVALID; }
+    if (n == 0) return GLP_OK;
+    if (n > (1ull << 30)) { glp_set_err(c, "glp_ed25519_half_scalars: bad size"); return GLP_E_INVALID; }
+    hipLaunchKernelGGL(glp_ed25519_half_scalars_kernel<0>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, d_k, n, d_out);
+    GLP_HIPCHK(c, hipGetLastError());
+    return GLP_OK;
+}

@@ -235,21 +235,29 @@ class DataCommitmentMapReduce:
                     f.cancel()
         return [p for _, p in done]
 
-    def _map_inputs_device(self, inputs_list):
+    def _map_inputs_device(self, inputs_list, resident=None):
         """_map_inputs with the witness programs evaluated on the device: chunks of device_witness_chunk input vectors on the main prover's
         stream (glp_witness_eval_device returns with the stream synchronised, so the map provers' streams may read the slab), then every prover
         places and proves its share of the chunk from the slab — no evaluator pool, no host copy of the variables.  A refused witness raises
-        ValueError naming its position in inputs_list."""
+        ValueError naming its position in inputs_list.
+        resident: inputs_list is then only a COUNT of leaves, and resident(lo, hi, buf) returns a device buffer holding the input rows of
+        leaves [lo, hi) (buf: the previous chunk's buffer, to reuse) — the input vectors never exist on the host."""
         from concurrent.futures import ThreadPoolExecutor
         n_workers = 1 + len(self.map_provers)
         chunk = self.device_witness_chunk
-        out, slab = [None] * len(inputs_list), None
+        if resident is not None:
+            inputs_list = range(int(inputs_list))
+        out, slab, d_in = [None] * len(inputs_list), None, None
         pool = ThreadPoolExecutor(n_workers - 1) if n_workers > 1 and len(inputs_list) > 1 else None
         try:
             for lo in range(0, len(inputs_list), chunk):
                 part = inputs_list[lo:lo + chunk]
                 try:
-                    slab = self.leaf_program.evaluate_device(self.prover, part, slab=slab)
+                    if resident is not None:
+                        d_in = resident(lo, lo + len(part), d_in)
+                        slab = self.leaf_program.evaluate_device(self.prover, len(part), slab=slab, d_inputs=d_in)
+                    else:
+                        slab = self.leaf_program.evaluate_device(self.prover, part, slab=slab)
                 except ValueError as e:
                     msg = str(e)
                     if msg.startswith("instance "):
@@ -285,6 +293,8 @@ class DataCommitmentMapReduce:
                 pool.shutdown(wait=True)
             if slab is not None:
                 slab.free()
+            if d_in is not None:
+                d_in.free()
         return out
 
     def prove_leaves(self, heights, data_roots):

@@ -901,12 +901,16 @@ class WitnessProgram:
             raise ValueError(f"glp_witness_plan_stats: {rc}")
         return dict(zip(("ops", "depth", "steps", "stream_bytes"), (int(x.value) for x in v)))
 
-    def evaluate_device(self, prover, inputs_batch, slab=None, segments=False):
+    def evaluate_device(self, prover, inputs_batch, slab=None, segments=False, d_inputs=None):
         """every variable of B input vectors computed ON THE DEVICE (glp_witness_eval_device: one workgroup per instance, level by level):
         returns a DeviceWitnessBatch owning the [B][n_values + fixed] slab.  ValueError with evaluate's texts (naming the instance) when an
         instance is refused.  slab: a DeviceWitnessBatch of an earlier call to reuse (same prover, at least as many rows).
-        segments=True: through the segmented plan — a workgroup per (instance, recorded segment), for recursion nodes; same values and verdicts."""
+        segments=True: through the segmented plan — a workgroup per (instance, recorded segment), for recursion nodes; same values and verdicts.
+        d_inputs: a device buffer that already holds the [B][n_inputs] input words (Prover.ed25519_leaf_inputs); inputs_batch is then the row
+        count B, nothing is uploaded and that buffer is read."""
         import ctypes
+        if d_inputs is not None:
+            return self._evaluate_device_resident(prover, int(inputs_batch), d_inputs, slab, segments)
         inp = np.ascontiguousarray(inputs_batch, dtype=np.uint64)
         if inp.ndim == 1:
             inp = inp.reshape(1, -1)
@@ -937,6 +941,33 @@ class WitnessProgram:
                 raise ValueError(f"instance {i}: the inputs do not satisfy the circuit ({what})")
             raise ValueError(f"instance {i}: witness program or inputs malformed")
         return slab
+
+    def _evaluate_device_resident(self, prover, B, d_inputs, slab, segments):
+        """evaluate_device on input rows that are already on the device"""
+        nbytes = getattr(d_inputs, "nbytes", None)
+        if nbytes is not None and nbytes < B * self.n_inputs * 8:
+            raise ValueError(f"the input buffer holds fewer than {B} rows of {self.n_inputs} inputs")
+        plan = self.plan(segments)
+        if slab is None or slab.prover is not prover or slab.rows < B or slab.program is not self or slab.buf.ptr is None:
+            slab = DeviceWitnessBatch(self, prover, B)
+        slab.B = B
+        if B == 0:
+            return slab
+        status = np.zeros(B, dtype=np.int32)
+        bad = np.zeros(B, dtype=np.uint64)
+        prover._chk(prover.lib.glp_witness_eval_device(prover.ctx, plan, _ptr(d_inputs), slab.buf.ptr, slab.stride, B, status.ctypes.data,
+                                                       bad.ctypes.data), "glp_witness_eval_device")
+        self._raise_refused(status, bad)
+        return slab
+
+    @staticmethod
+    def _raise_refused(status, bad):
+        for i in np.nonzero(status)[0].tolist():
+            if status[i] == -7:
+                what = ("a row input is out of range (a SHA word above 32 bits, a swap bit above 1)" if int(bad[i]) == 0xFFFFFFFFFFFFFFFF
+                        else f"copy constraint {int(bad[i])} fails")
+                raise ValueError(f"instance {i}: the inputs do not satisfy the circuit ({what})")
+            raise ValueError(f"instance {i}: witness program or inputs malformed")
 
     def inputs_from_words(self, word_lists):
         """the input vector of a program whose inputs were tagged (list number, word position) — e.g. the proofs a verifier circuit consumes —

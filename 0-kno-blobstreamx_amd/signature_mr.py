@@ -49,9 +49,14 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
     vote_format = None                              # a blobstream.VoteFormat in CanonicalVoteSetMapReduce
 
     def __init__(self, prover, poseidon_consts, msg_len=112, hash_offset=16, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False,
-                 device_witness_chunk=32, prove_batch=0, **kw):
+                 device_witness_chunk=32, prove_batch=0, device_inputs=False, **kw):
+        """device_inputs (default off; needs device_witness): the leaves' INPUT VECTORS are built on the device too — one
+        Prover.ed25519_leaf_inputs call per device_witness_chunk slots (the witness kernel, then the input kernel: limbs, t, the half-size scalar
+        hints), whose rows WitnessProgram.evaluate_device reads where they lie.  No record is downloaded and ed25519_circuit.witness_inputs is
+        not called; the same proofs, byte for byte."""
         if hash_offset + 32 > msg_len or hash_offset % 4 or msg_len % 4:
             raise ValueError("the vote bytes must hold a 32-byte block hash at a word-aligned offset")
+        self._set_device_inputs(device_inputs, device_witness)
         super().__init__(prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits, map_provers=map_provers,
                          device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch, **kw)     # kw: check_witness
         self.msg_len, self.hash_offset = int(msg_len), int(hash_offset)
@@ -106,6 +111,11 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         self.leaf_stats = dict(self.leaf_program.stats, field_products=st["stats"]["field_products"])
         self.record_seconds["leaf"] = round(time.perf_counter() - t0, 3)
 
+    def _set_device_inputs(self, device_inputs, device_witness):
+        if device_inputs and not device_witness:
+            raise ValueError("device_inputs needs device_witness=True: the rows it builds are read by the device evaluator")
+        self.device_inputs = bool(device_inputs)
+
     def _check_slot(self, pubkey, msg):
         if len(bytes(msg)) != self.msg_len or len(bytes(pubkey)) != 32:
             raise ValueError("vote bytes / key of another length than this circuit was recorded for")
@@ -140,6 +150,8 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
         from .ed25519_circuit import dummy_signature
         for i in range(lo, hi):
             self._check_slot(slots[0][i], slots[2][i])
+        if getattr(self, "device_inputs", False):
+            return self._map_device_inputs(slots, lo, hi)
         d_pub, d_sig, d_msg = dummy_signature(self._dummy_len())
         triples = [(slots[0][i], slots[1][i], slots[2][i]) if slots[3][i] else (d_pub, d_sig, d_msg) for i in range(lo, hi)]
         if any(t[1] is None or len(bytes(t[1])) != 64 for t in triples):
@@ -150,6 +162,38 @@ class SignatureSetMapReduce(DataCommitmentMapReduce):
             raise ValueError(f"the signatures of slots {bad[:8]} do not verify (GPU witness kernel)")
         return self._map_inputs([witness_inputs(slots[0][i], slots[1][i] if slots[3][i] else bytes(64), slots[2][i], slots[3][i], record=recs[i - lo],
                                                 vote_format=self.vote_format) for i in range(lo, hi)])
+
+    def _input_layout(self):
+        from . import ED25519_FORM_FLAGGED, ED25519_FORM_VOTE, Ed25519InputLayout
+        if self.vote_format is not None:
+            return Ed25519InputLayout(ED25519_FORM_VOTE, self.vote_format.min_len, self.vote_format.max_len, 1)
+        return Ed25519InputLayout(ED25519_FORM_FLAGGED, self.msg_len, self.msg_len, 1)
+
+    def _map_device_inputs(self, slots, lo, hi):
+        """_map with the input vectors built on the device (device_inputs): per chunk ONE glp_ed25519_leaf_inputs call, its rows read in place by
+        the device evaluator.  The refusals are _map's: a flagged slot the witness kernel rejects, a scalar without a half-size pair."""
+        from . import ED25519_IN_NO_PAIR, ED25519_IN_OK, ED25519_IN_REJECT
+        from .ed25519_circuit import dummy_signature
+        if any(slots[3][i] and (slots[1][i] is None or len(bytes(slots[1][i])) != 64) for i in range(lo, hi)):
+            raise ValueError("a flagged slot has no 64-byte signature")
+        layout, dummy = self._input_layout(), dummy_signature(self._dummy_len())
+        if layout.n_words() != self.leaf_program.n_inputs:
+            raise ValueError("the recorded leaf takes other inputs than the device builds")
+
+        def resident(a, b, buf):
+            ids = range(lo + a, lo + b)
+            buf, status = self.prover.ed25519_leaf_inputs(layout, [slots[0][i] for i in ids], [slots[1][i] if slots[3][i] else None for i in ids],
+                                                          [slots[2][i] for i in ids], [slots[3][i] for i in ids], dummy, out=buf)
+            bad = [lo + a + j for j in range(len(ids)) if status[j] == ED25519_IN_REJECT]
+            if bad:
+                raise ValueError(f"the signatures of slots {bad[:8]} do not verify (GPU witness kernel)")
+            for j in range(len(ids)):
+                if status[j] == ED25519_IN_NO_PAIR:
+                    raise ValueError(f"slot {lo + a + j}: no half-size scalar pair below 2^144 for this signature (probability ~2^-36)")
+                if status[j] != ED25519_IN_OK:
+                    raise ValueError(f"slot {lo + a + j}: vote bytes of another length than this circuit takes")
+            return buf
+        return self._map_inputs_device(hi - lo, resident=resident)
 
     def prove_set(self, pubkeys, signatures, msgs, flags):
         """one proof for a validator set's signatures: public = block hash (8 words), signer digest (4 words).  signatures[i] may be None where
@@ -268,7 +312,9 @@ class CanonicalVoteSetMapReduce(SignatureSetMapReduce):
     _NANOS = (0, 5, 300, 70_000, 3_000_000, 999_999_999)                      # varints of 0 (field omitted), 1, 2, 3, 4 and 5 bytes
 
     def __init__(self, prover, poseidon_consts, vote_format, chain_id="celestia", round=0, part_total=1, part_hash=bytes(32), seconds=1_700_000_000,
-                 fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False, device_witness_chunk=32, prove_batch=0, **kw):
+                 fan_in=8, num_queries=28, pow_bits=16, map_provers=(), device_witness=False, device_witness_chunk=32, prove_batch=0,
+                 device_inputs=False, **kw):
+        self._set_device_inputs(device_inputs, device_witness)
         DataCommitmentMapReduce.__init__(self, prover, poseidon_consts, leaf_blocks=1, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
                                          map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk,
                                          prove_batch=prove_batch, **kw)                                                 # kw: check_witness

@@ -582,6 +582,46 @@ int glp_sha512_trace(glp_ctx* ctx, const uint8_t* d_blocks, uint64_t n_msgs, uin
 int glp_ed25519_witness(glp_ctx* ctx, const uint8_t* d_pubs, const uint8_t* d_sigs, const uint8_t* d_msgs, uint32_t msg_stride,
                         const uint32_t* d_lens, uint64_t n, uint64_t* d_out);
 
+/* The INPUT VECTORS of the signature leaf on the device: row i of d_inputs is what ed25519_circuit.witness_inputs builds for slot i, word for
+ * word — the bytes of the statement's free inputs, the 24-bit limbs of x_A, x_R, t = h div L and k = h mod L (h = SHA-512(R || A || M)) and,
+ * with split_scalars, the half-size form's hints u[6] v[6] neg q1[7] w[11] q2[7] (u k = -+v mod 8L by Lagrange reduction of a 2-dimensional
+ * lattice; u S = q1 L + w; u k -+ v = q2 8L).  d_inputs ([n][input_stride] words, input_stride >= glp_ed25519_leaf_input_words) is what
+ * glp_witness_eval_device reads: nothing of a slot visits the host.
+ * form: GLP_ED25519_FORM_PLAIN    A[32] R[32] S[32] M[len] | limbs                          (msg_len_min = msg_len_max = len; d_flags, d_dummy NULL)
+ *       GLP_ED25519_FORM_FLAGGED  flag key[32] M[len] | R S of the VERIFIED triple | limbs    (msg_len_min = msg_len_max = len)
+ *       GLP_ED25519_FORM_VOTE     flag key[32] M zero-padded to msg_len_max, L, one-hot of L - msg_len_min [max - min + 1] | R S | limbs
+ * The verified triple of a slot is its own when d_flags[i] != 0 and the caller's dummy triple when it is 0: d_dummy = pub[32] | sig[64] |
+ * msg[msg_len_min], a constant of the circuit.  Two stream-ordered launches whatever n is: the kernel of glp_ed25519_witness over the slots'
+ * own triples into pool scratch, then the input kernel (one work-item per slot), which takes x_A, x_R, k of a flagged slot from its record and
+ * decodes / reduces the dummy's itself for an unflagged one.  ONE synchronise, after the copy of the statuses to h_status[n]:
+ *   GLP_ED25519_IN_OK       the row is written
+ *   GLP_ED25519_IN_REJECT   the record says invalid (a flagged signature that does not verify, an A or R that does not decode, S >= L)
+ *   GLP_ED25519_IN_NO_PAIR  no half-size pair below 2^144 (probability ~2^-36; the Python raises)
+ *   GLP_ED25519_IN_INVALID  d_lens[i] outside [msg_len_min, msg_len_max] or above msg_stride
+ * A row whose status is not OK is all zero: none is written partially.  glp_ed25519_last_input_counts reports the launches and synchronises
+ * of the LAST call on the ctx.  n == 0 is GLP_OK.  GLP_E_INVALID for a null argument, a layout no statement has, or a stride below the row.
+ * glp_ed25519_leaf_input_words needs no GPU and no ctx. */
+#define GLP_ED25519_FORM_PLAIN 0
+#define GLP_ED25519_FORM_FLAGGED 1
+#define GLP_ED25519_FORM_VOTE 2
+#define GLP_ED25519_IN_OK 0
+#define GLP_ED25519_IN_REJECT 1
+#define GLP_ED25519_IN_NO_PAIR 2
+#define GLP_ED25519_IN_INVALID 3
+typedef struct {
+    uint32_t form;
+    uint32_t msg_len_min, msg_len_max;
+    uint32_t split_scalars;
+} glp_ed25519_input_layout;
+int glp_ed25519_leaf_input_words(const glp_ed25519_input_layout* layout, uint64_t* n_words);
+int glp_ed25519_leaf_inputs(glp_ctx* ctx, const glp_ed25519_input_layout* layout, const uint8_t* d_pubs, const uint8_t* d_sigs,
+                            const uint8_t* d_msgs, uint32_t msg_stride, const uint32_t* d_lens, const uint8_t* d_flags, const uint8_t* d_dummy,
+                            uint64_t n, uint64_t* d_inputs, size_t input_stride, int32_t* h_status);
+int glp_ed25519_last_input_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
+/* The reduction alone: d_k [n][4] little-endian scalars -> d_out [n][8] = u[3] v[3] neg status (OK, NO_PAIR, or INVALID for k >= L; u, v are
+ * zero unless OK).  ed25519_circuit.half_size_pair on the device.  One launch, stream-ordered (glp_sync before reading d_out). */
+int glp_ed25519_half_scalars(glp_ctx* ctx, const uint64_t* d_k, uint64_t n, uint64_t* d_out);
+
 /* Tendermint "simple" Merkle root (RFC 6962 prefixes) of n leaves of leaf_len (<= 118) bytes each:
  * the validator-set / header hashing of BASELINE configs[0].  Synchronous; h_root32 = 32 bytes. */
 int glp_tm_merkle_root(glp_ctx* ctx, const uint8_t* d_leaves, uint32_t leaf_len, uint64_t n, uint8_t* h_root32);
