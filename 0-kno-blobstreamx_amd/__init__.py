@@ -152,6 +152,111 @@ class FriStatement(ctypes.Structure):
                 "caps": caps, "openings": [(int(op[2 * k]), int(op[2 * k + 1])) for k in range(self.n_openings)]}
 
 
+class VerifyVerdict(ctypes.Structure):
+    """one proof's verdict of a batched verification (glp_verify_verdict)"""
+    _fields_ = [("status", ctypes.c_int32), ("reason", ctypes.c_uint32), ("query", ctypes.c_uint32), ("on_device", ctypes.c_uint32)]
+
+
+NOT_WORDS = "proof length is not a whole number of u64 words"
+
+
+class _ProofBatch:
+    """B proofs as the batched verifiers take them: one 8-byte aligned copy each, a pointer table and a length table.  A proof that is not a
+    whole number of words is never handed over: its verdict is the wrappers' own (as Prover._verify gives it)."""
+
+    def __init__(self, proofs):
+        self.raw = [bytes(p) for p in proofs]
+        self.sent = [i for i, r in enumerate(self.raw) if r and len(r) % 8 == 0]
+        self.words = [np.frombuffer(self.raw[i], dtype="<u8").copy() for i in self.sent]
+        self.ptrs = (ctypes.c_void_p * max(1, len(self.sent)))(*[w.ctypes.data for w in self.words])
+        self.lens = (ctypes.c_size_t * max(1, len(self.sent)))(*[w.nbytes for w in self.words])
+        self.verdicts = (VerifyVerdict * max(1, len(self.sent)))()
+
+    def results(self, lib):
+        """[(ok, reason text or None, failing query or None)] in the callers' order"""
+        out = [(False, NOT_WORDS, None)] * len(self.raw)
+        for k, i in enumerate(self.sent):
+            v = self.verdicts[k]
+            if v.status == 0:
+                out[i] = (True, None, None)
+            else:
+                out[i] = (False, lib.glp_verify_reason_text(v.reason).decode(), None if v.query == 0xFFFFFFFF else int(v.query))
+        return out
+
+    def spread(self, rows, fill):
+        """per-sent-proof rows back into the callers' order"""
+        out = [fill] * len(self.raw)
+        for k, i in enumerate(self.sent):
+            out[i] = rows[k]
+        return out
+
+
+def _publics_arg(publics, batch):
+    """(pointer-or-None, n_public, keepalive) for [B][n_public] expected public inputs; None / UNBOUND = do not bind"""
+    if publics is None or (isinstance(publics, str) and publics == UNBOUND):
+        return None, 0, None
+    rows = [[int(v) for v in publics[i]] for i in batch.sent]
+    n_pub = len(rows[0]) if rows else 0
+    if any(len(r) != n_pub for r in rows):
+        raise GlpError("verify_batch: every proof of a batch takes the same number of expected public inputs")
+    a = np.ascontiguousarray(rows, dtype=np.uint64).reshape(len(rows), n_pub)
+    keep = a if a.size else np.zeros(1, dtype=np.uint64)
+    return keep.ctypes.data, n_pub, keep
+
+
+def _cap_arg(circuit_cap, who):
+    if circuit_cap is None:
+        raise GlpError(f"{who}: circuit_cap is required (pass UNBOUND to skip the binding explicitly)")
+    return None if isinstance(circuit_cap, str) and circuit_cap == UNBOUND else np.ascontiguousarray(circuit_cap, dtype=np.uint64)
+
+
+def plonk_verify_batch_host(constants, proofs, circuit_cap, min_queries=None, min_pow_bits=None, publics=None, want_digests=False,
+                            want_counts=False):
+    """B circuit proofs through the batched verifier WITHOUT a GPU (glp_plonk_verify_batch_host): the same host phase and the same item
+    bodies as Prover.plonk_verify_batch, run one after the other.  Returns [(ok, reason, query)]; with want_digests / want_counts a tuple
+    that also carries the [B] digests (None where the header does not parse) / (n_on_device, n_fallback)."""
+    lib = load_library()
+    rc, circ, diag = (np.ascontiguousarray(a, dtype=np.uint64) for a in constants)
+    if rc.size != 360 or circ.size != 12 or diag.size != 12:
+        raise GlpError("Poseidon constants: 360 round constants, 12 + 12 MDS entries")
+    b = _ProofBatch(proofs)
+    cap = _cap_arg(circuit_cap, "plonk_verify_batch_host")
+    pp, pn, keep = _publics_arg(publics, b)
+    dg = np.zeros((max(1, len(b.sent)), 4), dtype=np.uint64)
+    nd, nf = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    code = lib.glp_plonk_verify_batch_host(rc.ctypes.data, circ.ctypes.data, diag.ctypes.data, b.ptrs, b.lens, len(b.sent),
+                                           cap.ctypes.data if cap is not None else None, cap.size if cap is not None else 0, pp, pn,
+                                           DEFAULT_MIN_QUERIES if min_queries is None else min_queries,
+                                           DEFAULT_MIN_POW_BITS if min_pow_bits is None else min_pow_bits, b.verdicts, dg.ctypes.data,
+                                           ctypes.byref(nd), ctypes.byref(nf))
+    if code != 0:
+        raise GlpError(f"glp_plonk_verify_batch_host: {_ERR.get(code, code)}")
+    out = (b.results(lib),)
+    if want_digests:
+        out += (b.spread([[int(v) for v in row] if row.any() else None for row in dg[:len(b.sent)]], None),)
+    if want_counts:
+        out += ((int(nd.value), int(nf.value)),)
+    return out[0] if len(out) == 1 else out
+
+
+def fri_verify_batch_host(constants, proofs, min_queries=None, min_pow_bits=None, min_rate_bits=None, want_counts=False):
+    """B stand-alone FRI proofs through the batched verifier without a GPU (glp_fri_verify_batch_host): [(ok, reason, query)]"""
+    lib = load_library()
+    rc, circ, diag = (np.ascontiguousarray(a, dtype=np.uint64) for a in constants)
+    if rc.size != 360 or circ.size != 12 or diag.size != 12:
+        raise GlpError("Poseidon constants: 360 round constants, 12 + 12 MDS entries")
+    b = _ProofBatch(proofs)
+    nd, nf = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    code = lib.glp_fri_verify_batch_host(rc.ctypes.data, circ.ctypes.data, diag.ctypes.data, b.ptrs, b.lens, len(b.sent),
+                                         DEFAULT_MIN_QUERIES if min_queries is None else min_queries,
+                                         DEFAULT_MIN_POW_BITS if min_pow_bits is None else min_pow_bits,
+                                         DEFAULT_MIN_RATE_BITS if min_rate_bits is None else min_rate_bits, b.verdicts, None,
+                                         ctypes.byref(nd), ctypes.byref(nf))
+    if code != 0:
+        raise GlpError(f"glp_fri_verify_batch_host: {_ERR.get(code, code)}")
+    return (b.results(lib), (int(nd.value), int(nf.value))) if want_counts else b.results(lib)
+
+
 # security parameters every verify wrapper requires unless the caller says otherwise: 28 queries at rate 1/8 + 16 bits of
 # proof of work (the prover's defaults).  A proof made with weaker parameters is REJECTED by default.
 DEFAULT_MIN_QUERIES = 28
@@ -280,6 +385,16 @@ def load_library():
         "glp_plonk_last_check_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "glp_plonk_verify_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_uint32,
                                                ctypes.c_uint32]),
+        "glp_plonk_verify_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_uint32,
+                                                  ctypes.c_uint32, _vp, _vp]),
+        "glp_fri_verify_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
+        "glp_verify_reason_text": (ctypes.c_char_p, [ctypes.c_uint32]),
+        "glp_verify_last_batch_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 4),
+        "glp_plonk_verify_batch_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                                       ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, ctypes.POINTER(ctypes.c_uint32),
+                                                       ctypes.POINTER(ctypes.c_uint32)]),
+        "glp_fri_verify_batch_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     _vp, _vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
         "glp_plonk_verify_host_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]),
         "glp_plonk_proof_public_inputs": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, ctypes.POINTER(ctypes.c_size_t)]),
@@ -1000,6 +1115,44 @@ class Prover:
                                                                       cap.size if cap is not None else 0, pp, pn, min_queries, min_pow_bits),
                             proof)
 
+    def plonk_verify_batch(self, proofs, circuit_cap, min_queries=DEFAULT_MIN_QUERIES, min_pow_bits=DEFAULT_MIN_POW_BITS, publics=None,
+                           want_digests=False):
+        """B circuit proofs in one call, their query phases on the device (glp_plonk_verify_batch; opt-in).  circuit_cap as for plonk_verify
+        (required, UNBOUND skips the binding); publics: None / UNBOUND = do not bind, else one row of expected public inputs per proof.
+        Returns [(ok, reason text, failing query)] — what plonk_verify and last_reject give proof by proof; with want_digests also the
+        proofs' digests (proof_digest), None where the header does not parse."""
+        b = _ProofBatch(proofs)
+        cap = _cap_arg(circuit_cap, "plonk_verify_batch")
+        pp, pn, keep = _publics_arg(publics, b)
+        dg = np.zeros((max(1, len(b.sent)), 4), dtype=np.uint64)
+        self._chk(self.lib.glp_plonk_verify_batch(self.ctx, b.ptrs, b.lens, len(b.sent), cap.ctypes.data if cap is not None else None,
+                                                  cap.size if cap is not None else 0, pp, pn, min_queries, min_pow_bits, b.verdicts,
+                                                  dg.ctypes.data), "glp_plonk_verify_batch")
+        res = b.results(self.lib)
+        if want_digests:
+            return res, b.spread([[int(v) for v in row] if row.any() else None for row in dg[:len(b.sent)]], None)
+        return res
+
+    def fri_verify_batch(self, proofs, min_queries=DEFAULT_MIN_QUERIES, min_pow_bits=DEFAULT_MIN_POW_BITS, min_rate_bits=DEFAULT_MIN_RATE_BITS,
+                         want_statements=False):
+        """B stand-alone FRI proofs in one call (glp_fri_verify_batch): [(ok, reason text, failing query)]; with want_statements also what
+        each accepted proof proves (as fri_verify leaves it in last_statement), None for a refused one"""
+        b = _ProofBatch(proofs)
+        sts = (FriStatement * max(1, len(b.sent)))()
+        self._chk(self.lib.glp_fri_verify_batch(self.ctx, b.ptrs, b.lens, len(b.sent), min_queries, min_pow_bits, min_rate_bits, b.verdicts,
+                                                sts), "glp_fri_verify_batch")
+        res = b.results(self.lib)
+        if want_statements:
+            rows = [sts[k].as_dict(b.raw[i]) if b.verdicts[k].status == 0 else None for k, i in enumerate(b.sent)]
+            return res, b.spread(rows, None)
+        return res
+
+    def verify_last_batch_counts(self):
+        """what the last *_verify_batch on this ctx issued: dict launches, host_syncs, on_device, fallback"""
+        v = [ctypes.c_uint32(0) for _ in range(4)]
+        self._chk(self.lib.glp_verify_last_batch_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_verify_last_batch_counts")
+        return dict(zip(("launches", "host_syncs", "on_device", "fallback"), (int(x.value) for x in v)))
+
     def proof_digest(self, proof):
         """4-word digest of a circuit proof's statement and commitments (glp_plonk_proof_digest): the aggregation tree's leaf"""
         words = np.frombuffer(bytes(proof), dtype="<u8").copy()
@@ -1242,6 +1395,15 @@ class PlonkCircuit:
         if public is None and self.n_public:
             raise GlpError("verify: this circuit has public inputs — pass the expected ones (or UNBOUND)")
         return self.prover.plonk_verify(proof, self.cap(), min_queries, min_pow_bits, public=public)
+
+    def verify_batch(self, proofs, min_queries=28, min_pow_bits=16, publics=None, want_digests=False):
+        """B proofs bound to this circuit in one call (Prover.plonk_verify_batch); publics: one row of expected public inputs per proof
+        (None: the circuit has none; UNBOUND: any)"""
+        if publics is None and self.n_public:
+            raise GlpError("verify_batch: this circuit has public inputs — pass the expected ones (or UNBOUND)")
+        if publics is None:
+            publics = [[] for _ in proofs]
+        return self.prover.plonk_verify_batch(proofs, self.cap(), min_queries, min_pow_bits, publics=publics, want_digests=want_digests)
 
     def _public_words(self, public):
         pub = np.ascontiguousarray([] if public is None else [int(v) for v in public], dtype=np.uint64)

@@ -61,6 +61,9 @@ struct glp_ctx {
     uint32_t place_counts[2] = {0, 0};
     // what the last glp_plonk_check_witness[_batch] issued: kernel launches (an NTT call counts as one), stream synchronises (glp_plonk_last_check_counts)
     uint32_t check_counts[2] = {0, 0};
+    // what the last glp_*_verify_batch issued: kernel launches, stream synchronises, proofs whose queries ran as items, proofs verified in place
+    // (glp_verify_last_batch_counts)
+    uint32_t verify_batch_counts[4] = {0, 0, 0, 0};
     // pinned staging of that call's slab-row table (the caller's h_rows may be gone before the copy runs: the call need not synchronise);
     // place_ev follows the copy, and the next call waits for it before it overwrites the staging
     uint32_t* place_rows_host = nullptr;

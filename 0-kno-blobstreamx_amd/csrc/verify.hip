@@ -5,13 +5,15 @@
 // reference file:line NONE — the mount is empty): plonky2::plonk::verifier::verify,
 // fri::verifier::verify_fri_proof.
 //
-// Host C++ on purpose: a verification is ~5,000 Poseidon permutations and a few hundred
-// extension-field operations — transcript-sized work with a serial dependency chain, the same
-// reason the prover's challenger runs on the host.  It shares no arithmetic with the GPU
-// kernels' LDS/launch structure but uses the same field primitives (gl_field.cuh, portable forms)
-// and the same permutation body (hash_kernels.cuh) with the constants injected into the ctx.
-// tests/fri_verifier.py and tests/plonk_ref.py (Python big-int) stay the independent checkers of
-// both the prover and this file.
+// The single verifiers are host C++ (verify_plan.h): a verification is ~5,000 Poseidon permutations and a few hundred
+// extension-field operations.  Host on purpose for the TRANSCRIPT and the PLONK identity — a serial dependency
+// chain, the same reason the prover's challenger runs on the host.  Not so for the queries: the loop over the queries
+// is independent per (proof, query) and is most of the permutations, and the batched entry points at the end of the
+// first half of this file (glp_plonk_verify_batch, glp_fri_verify_batch) run it on the device for
+// B proofs at once (verify_batch_kernels.cuh), the host keeping the serial part per proof.  Both use the same field
+// primitives (gl_field.cuh, portable forms) and the same permutation body (hash_kernels.cuh) with the constants
+// injected into the ctx.  tests/fri_verifier.py and tests/plonk_ref.py (Python big-int) stay the independent
+// checkers of both the prover and this file.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -24,523 +26,191 @@
 #include "plonk_gates.h"
 #include "nnf25519.h"
 #include "witness_plan.h"
+#include "verify_plan.h"
+#include "verify_batch_kernels.cuh"
+
+using namespace glp_verify;
 
 namespace {
-const u64 FRI_TAG = 0x32304952464C4747ull;
-const u64 PLONK_TAG = 0x32304B4C504C4747ull;   // "GGLPLK02"
-const u32 CHUNK = 8, NCHAL = 2;
-
-struct Reject {
-    glp_ctx* c;          // reason goes to the ctx's error text ...
-    char* buf;           // ... or, for the ctx-less entry points, to the caller's buffer (may be null)
-    size_t n;
-    int fail(const char* why) {
-        if (c) glp_set_err(c, "proof rejected: %s", why);
-        else if (buf && n) snprintf(buf, n, "proof rejected: %s", why);
-        return GLP_E_REJECT;
-    }
-};
-
-struct Hasher {
-    std::vector<u64> consts;
-    bool small_mds;
-    void permute(u64 (&s)[12]) const {
-        GlpPoseidonConsts k{consts.data(), consts.data() + 360, consts.data() + 372, nullptr, nullptr};
-        if (small_mds) glp_poseidon_permute<true>(s, k);
-        else glp_poseidon_permute<false>(s, k);
-    }
-    // digest of a leaf: the zero-padded leaf itself up to 4 elements, else the overwrite-mode sponge
-    void hash_or_noop(const u64* e, size_t len, u64 (&out)[4]) const {
-        if (len <= 4) {
-            for (size_t i = 0; i < 4; i++) out[i] = i < len ? e[i] : 0;
-            return;
-        }
-        u64 s[12] = {0};
-        for (size_t off = 0; off < len; off += 8) {
-            const size_t m = len - off < 8 ? len - off : 8;
-            for (size_t i = 0; i < m; i++) s[i] = e[off + i];
-            permute(s);
-        }
-        for (int i = 0; i < 4; i++) out[i] = s[i];
-    }
-    void two_to_one(const u64* l, const u64* r, u64 (&out)[4]) const {
-        u64 s[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
-        permute(s);
-        for (int i = 0; i < 4; i++) out[i] = s[i];
-    }
-};
-
-inline bool ext_eq(gl_ext2 x, gl_ext2 y) { return x.a == y.a && x.b == y.b; }
-inline gl_ext2 ext_inv(gl_ext2 x) {
-    const u64 nrm = gl_sub(gl_mul(x.a, x.a), gl_mul(7, gl_mul(x.b, x.b)));   // a^2 - 7 b^2
-    const u64 ni = gl_inv(nrm);
-    return {gl_mul(x.a, ni), gl_mul(gl_neg(x.b), ni)};
-}
-inline u64 bitrev(u64 v, u32 bits) {
-    u64 r = 0;
-    for (u32 i = 0; i < bits; i++) r |= ((v >> i) & 1ull) << (bits - 1 - i);
-    return r;
-}
-
-struct Reader {
-    const u64* w;
-    size_t n, pos;
-    bool take(size_t k, const u64** out) {
-        if (k > n - pos) return false;
-        *out = w + pos;
-        pos += k;
-        return true;
-    }
-};
-
-bool merkle_check(const Hasher& h, const u64 (&leaf_digest)[4], u64 index, const u64* path, u32 path_len, const u64* cap, u64 cap_len) {
-    u64 cur[4] = {leaf_digest[0], leaf_digest[1], leaf_digest[2], leaf_digest[3]};
-    for (u32 lvl = 0; lvl < path_len; lvl++) {
-        u64 nxt[4];
-        if (((index >> lvl) & 1ull) == 0) h.two_to_one(cur, path + 4 * lvl, nxt);
-        else h.two_to_one(path + 4 * lvl, cur, nxt);
-        memcpy(cur, nxt, sizeof(cur));
-    }
-    const u64 ci = index >> path_len;
-    return ci < cap_len && memcmp(cur, cap + 4 * ci, sizeof(cur)) == 0;
-}
-
-struct FriInfo {
-    u32 log_n = 0, rb = 0, cap0 = 0, n_pts = 0, nb = 0, nq = 0, pow_bits = 0;
-    u64 shift = 0;
-    u64 mults[4] = {0, 0, 0, 0};
-    size_t caps_off = 0, openings_off = 0;       // word offsets inside the proof
-    gl_ext2 zeta{0, 0};
-    std::vector<gl_ext2> points;                 // zeta * mult[p]
-    std::vector<u64> n_polys, masks;
-    std::vector<const u64*> caps;                // per batch, 4 << cap0 words inside the proof
-    std::vector<std::pair<u32, u32>> order;      // (point, batch) in opening order
-    std::vector<size_t> open_off;                // offset into openings per order entry
-    std::vector<gl_ext2> openings;
-};
-
-// The FRI opening proof starting at rd.pos, continuing the transcript `ch` (fresh for a stand-alone proof).
-int fri_verify(Reject rj, const Hasher& h, glp_challenger& ch, Reader& rd, bool allow_trailing, u32 min_queries, u32 min_pow_bits,
-               u32 min_rate_bits, FriInfo& fi) {
-    const u64* hd;
-    if (!rd.take(11, &hd)) return rj.fail("truncated");
-    const u64 tag = hd[0], log_n = hd[1], rb = hd[2], cap0 = hd[3], a = hd[4], fb = hd[5], nq = hd[6], pow_bits = hd[7], shift = hd[8],
-              nb = hd[9], n_pts = hd[10];
-    if (tag != FRI_TAG) return rj.fail("bad tag");
-    if (n_pts < 1 || n_pts > 4 || nb == 0 || nb > 64) return rj.fail("bad header");
-    if (log_n > 32 || rb > 8 || log_n + rb > 32 || a == 0 || a > 8 || fb > 12 || nq == 0 || nq > 1024 || pow_bits > 40 || shift == 0 ||
-        shift >= GL_P)
-        return rj.fail("header out of range");
-    // rate 1 (rate_bits = 0) is no proximity test at all: every word of length n is a codeword of degree < n, so ANY
-    // claimed opening passes.  Never accepted, whatever the caller asks for.
-    if (rb == 0) return rj.fail("rate_bits = 0: a rate-1 code proves nothing");
-    if (nq < min_queries || pow_bits < min_pow_bits) return rj.fail("fewer queries or less proof of work than required");
-    if (rb < min_rate_bits) return rj.fail("lower code rate (rate_bits) than required");
-    const u64 *mults, *pm;
-    if (!rd.take(n_pts, &mults) || !rd.take(2 * nb, &pm)) return rj.fail("truncated");
-    bool first_point_used = false;
-    for (u64 b = 0; b < nb; b++) {
-        const u64 np = pm[2 * b], m = pm[2 * b + 1];
-        if (np == 0 || np > (1u << 20) || m == 0 || (m >> n_pts)) return rj.fail("bad open masks");
-        if (m & 1) first_point_used = true;
-    }
-    if (!first_point_used) return rj.fail("bad open masks");
-    for (u64 p = 0; p < n_pts; p++)
-        if (mults[p] == 0 || mults[p] >= GL_P) return rj.fail("bad point multiplier");
-    for (int i = 0; i < 11; i++) ch.observe(hd[i] % GL_P);
-    for (u64 i = 0; i < n_pts; i++) ch.observe(mults[i]);
-    for (u64 i = 0; i < 2 * nb; i++) ch.observe(pm[i]);
-    const u32 log_N = (u32)(log_n + rb);
-    const u64 N = 1ull << log_N;
-    if (cap0 > log_N) return rj.fail("cap height");
-    const u32 L = log_n > fb ? (u32)((log_n - fb) / a) : 0;
-    const u32 final_bits = (u32)(log_n - a * L);
-    fi.log_n = (u32)log_n; fi.rb = (u32)rb; fi.cap0 = (u32)cap0; fi.n_pts = (u32)n_pts; fi.nb = (u32)nb; fi.nq = (u32)nq; fi.pow_bits = (u32)pow_bits;
-    fi.shift = shift;
-    for (u64 p = 0; p < n_pts; p++) fi.mults[p] = mults[p];
-    fi.caps_off = rd.pos;
-    for (u64 b = 0; b < nb; b++) {
-        const u64* cp;
-        if (!rd.take((size_t)4 << cap0, &cp)) return rj.fail("truncated");
-        for (size_t i = 0; i < ((size_t)4 << cap0); i++) {
-            if (cp[i] >= GL_P) return rj.fail("non-canonical cap");
-            ch.observe(cp[i]);
-        }
-        fi.caps.push_back(cp);
-        fi.n_polys.push_back(pm[2 * b]);
-        fi.masks.push_back(pm[2 * b + 1]);
-    }
-    fi.zeta = ch.ext_challenge();
-    size_t total = 0;
-    for (u32 p = 0; p < n_pts; p++)
-        for (u32 b = 0; b < nb; b++)
-            if ((fi.masks[b] >> p) & 1) {
-                fi.order.push_back({p, b});
-                fi.open_off.push_back(total);
-                total += fi.n_polys[b];
-            }
-    const u64* op;
-    fi.openings_off = rd.pos;
-    if (!rd.take(2 * total, &op)) return rj.fail("truncated");
-    fi.openings.resize(total);
-    for (size_t k = 0; k < total; k++) {
-        if (op[2 * k] >= GL_P || op[2 * k + 1] >= GL_P) return rj.fail("non-canonical opening");
-        ch.observe(op[2 * k]);
-        ch.observe(op[2 * k + 1]);
-        fi.openings[k] = {op[2 * k], op[2 * k + 1]};
-    }
-    const gl_ext2 alpha = ch.ext_challenge();
-    std::vector<gl_ext2> apow(total);
-    apow[0] = {1, 0};
-    for (size_t k = 1; k < total; k++) apow[k] = gl_ext_mul(apow[k - 1], alpha);
-    std::vector<gl_ext2> Ys(n_pts, gl_ext2{0, 0});
-    std::vector<bool> pt_used(n_pts, false);
-    fi.points.resize(n_pts);
-    for (u32 p = 0; p < n_pts; p++) fi.points[p] = gl_ext_scale(fi.zeta, mults[p]);
-    {
-        size_t kk = 0;
-        for (auto& pb : fi.order) {
-            pt_used[pb.first] = true;
-            for (u64 j = 0; j < fi.n_polys[pb.second]; j++, kk++) Ys[pb.first] = gl_ext_add(Ys[pb.first], gl_ext_mul(apow[kk], fi.openings[kk]));
-        }
-    }
-    std::vector<const u64*> layer_caps(L);
-    std::vector<gl_ext2> betas(L);
-    std::vector<u32> layer_log(L), layer_caph(L);
-    {
-        u32 log_len = log_N;
-        for (u32 l = 0; l < L; l++) {
-            const u32 log_leaves = log_len - (u32)a;
-            const u32 chh = cap0 < log_leaves ? (u32)cap0 : log_leaves;
-            const u64* cp;
-            if (!rd.take((size_t)4 << chh, &cp)) return rj.fail("truncated");
-            for (size_t i = 0; i < ((size_t)4 << chh); i++) {
-                if (cp[i] >= GL_P) return rj.fail("non-canonical layer cap");
-                ch.observe(cp[i]);
-            }
-            layer_caps[l] = cp;
-            betas[l] = ch.ext_challenge();
-            layer_log[l] = log_len;
-            layer_caph[l] = chh;
-            log_len -= (u32)a;
-        }
-    }
-    const u64* fin;
-    if (!rd.take((size_t)2 << final_bits, &fin)) return rj.fail("truncated");
-    for (size_t i = 0; i < ((size_t)2 << final_bits); i++) {
-        if (fin[i] >= GL_P) return rj.fail("non-canonical final polynomial");
-        ch.observe(fin[i]);
-    }
-    u64 seed[4];
-    for (int i = 0; i < 4; i++) seed[i] = ch.challenge();
-    const u64* noncep;
-    if (!rd.take(1, &noncep)) return rj.fail("truncated");
-    const u64 nonce = noncep[0] % GL_P;
-    if (pow_bits) {
-        u64 s[12] = {seed[0], seed[1], seed[2], seed[3], nonce, 0, 0, 0, 0, 0, 0, 0};
-        h.permute(s);
-        if (s[0] >> (64 - pow_bits)) return rj.fail("proof of work failed");
-    }
-    ch.observe(nonce);
-    std::vector<u64> idxs(nq);
-    for (u64 q = 0; q < nq; q++) idxs[q] = ch.challenge() & (N - 1);
-
-    const u64 w_N = gl_root_of_unity(log_N);
-    const u64 inv2 = gl_inv(2);
-    std::vector<gl_ext2> accs(n_pts), vals, nxt;
-    for (u64 q = 0; q < nq; q++) {
-        const u64* ip;
-        if (!rd.take(1, &ip)) return rj.fail("truncated");
-        const u64 idx = ip[0];
-        if (idx != idxs[q]) return rj.fail("query index does not match the transcript");
-        const u64 x = gl_mul(shift, gl_pow(w_N, bitrev(idx, log_N)));
-        std::vector<const u64*> leaves(nb);
-        for (u32 b = 0; b < nb; b++) {
-            const u64 *leaf, *path;
-            if (!rd.take(fi.n_polys[b], &leaf) || !rd.take((size_t)4 * (log_N - cap0), &path)) return rj.fail("truncated");
-            for (u64 j = 0; j < fi.n_polys[b]; j++)
-                if (leaf[j] >= GL_P) return rj.fail("non-canonical leaf");
-            u64 dg[4];
-            h.hash_or_noop(leaf, fi.n_polys[b], dg);
-            if (!merkle_check(h, dg, idx, path, (u32)(log_N - cap0), fi.caps[b], 1ull << cap0)) return rj.fail("Merkle path does not lead to the cap");
-            leaves[b] = leaf;
-        }
-        for (u32 p = 0; p < n_pts; p++) accs[p] = {0, 0};
-        {
-            size_t k = 0;
-            for (auto& pb : fi.order)
-                for (u64 j = 0; j < fi.n_polys[pb.second]; j++, k++) accs[pb.first] = gl_ext_add(accs[pb.first], gl_ext_scale(apow[k], leaves[pb.second][j]));
-        }
-        gl_ext2 cur{0, 0};
-        for (u32 p = 0; p < n_pts; p++)
-            if (pt_used[p]) {
-                const gl_ext2 den = gl_ext_sub(gl_ext2{x, 0}, fi.points[p]);
-                if (den.a == 0 && den.b == 0) return rj.fail("query point equals an opening point");
-                cur = gl_ext_add(cur, gl_ext_mul(gl_ext_sub(accs[p], Ys[p]), ext_inv(den)));
-            }
-        u64 sh = shift;
-        for (u32 l = 0; l < L; l++) {
-            const u32 ll = layer_log[l];
-            const u64 *leaf, *path;
-            const u32 log_leaves = ll - (u32)a;
-            if (!rd.take((size_t)2 << a, &leaf) || !rd.take((size_t)4 * (log_leaves - layer_caph[l]), &path)) return rj.fail("truncated");
-            vals.assign((size_t)1 << a, gl_ext2{0, 0});
-            for (size_t j = 0; j < ((size_t)1 << a); j++) {
-                if (leaf[2 * j] >= GL_P || leaf[2 * j + 1] >= GL_P) return rj.fail("non-canonical layer leaf");
-                vals[j] = {leaf[2 * j], leaf[2 * j + 1]};
-            }
-            const u64 p_l = idx >> (a * l);
-            const u64 leaf_idx = p_l >> a;
-            if (!ext_eq(vals[p_l & ((1ull << a) - 1)], cur)) return rj.fail("a layer value does not continue the fold");
-            u64 dg[4];
-            h.hash_or_noop(leaf, (size_t)2 << a, dg);
-            if (!merkle_check(h, dg, leaf_idx, path, log_leaves - layer_caph[l], layer_caps[l], 1ull << layer_caph[l])) return rj.fail("layer Merkle path does not lead to the cap");
-            gl_ext2 beta = betas[l];
-            u64 base = leaf_idx << a;
-            u32 cl = ll;
-            for (u64 s = 0; s < a; s++) {
-                const u64 wl = gl_root_of_unity(cl);
-                nxt.resize(vals.size() / 2);
-                for (size_t i = 0; i < vals.size() / 2; i++) {
-                    const u64 xi = gl_mul(sh, gl_pow(wl, bitrev(base + 2 * i, cl)));
-                    const gl_ext2 f0 = vals[2 * i], f1 = vals[2 * i + 1];
-                    const gl_ext2 sm = gl_ext_scale(gl_ext_add(f0, f1), inv2);
-                    const gl_ext2 d = gl_ext_scale(gl_ext_sub(f0, f1), gl_mul(inv2, gl_inv(xi)));
-                    nxt[i] = gl_ext_add(sm, gl_ext_mul(beta, d));
-                }
-                vals.swap(nxt);
-                base >>= 1;
-                cl -= 1;
-                beta = gl_ext_mul(beta, beta);
-                sh = gl_mul(sh, sh);
-            }
-            cur = vals[0];
-        }
-        const u32 fl = (u32)(log_N - a * L);
-        const u64 xf = gl_mul(sh, gl_pow(gl_root_of_unity(fl), bitrev(idx >> (a * L), fl)));
-        gl_ext2 ev{0, 0};
-        for (size_t j = (size_t)1 << final_bits; j-- > 0;) ev = gl_ext_add(gl_ext_scale(ev, xf), gl_ext2{fin[2 * j], fin[2 * j + 1]});
-        if (!ext_eq(ev, cur)) return rj.fail("final polynomial mismatch");
-    }
-    if (rd.pos != rd.n && !allow_trailing) return rj.fail("trailing data in proof");
-    return GLP_OK;
-}
-
-void init_hasher(const std::vector<u64>& consts, bool small_mds, Hasher& h, glp_challenger& ch) {
-    h.consts = consts;
-    h.small_mds = small_mds;
-    memset(ch.state, 0, sizeof(ch.state));
-    ch.n_in = ch.n_out = 0;
-    ch.consts = consts;
-    ch.small_mds = small_mds;
-}
 bool make_hasher(glp_ctx* c, Hasher& h, glp_challenger& ch) {
     if (!c->hash || !c->hash->have_consts) { glp_set_err(c, "Poseidon constants not set (glp_set_poseidon_constants)"); return false; }
     init_hasher(c->hash->h_consts, c->hash->small_mds, h, ch);
     return true;
 }
-// constants passed explicitly (the ctx-less entry points): same validity rules as glp_set_poseidon_constants
-bool make_hasher_from(const u64* rc, const u64* circ, const u64* diag, Hasher& h, glp_challenger& ch) {
-    if (!rc || !circ || !diag) return false;
-    std::vector<u64> all(384);
-    for (int i = 0; i < 360; i++) { if (rc[i] >= GL_P) return false; all[i] = rc[i]; }
-    unsigned __int128 sum = 0;
-    u64 maxdiag = 0;
-    bool small = true;
-    for (int i = 0; i < 12; i++) {
-        if (circ[i] >= GL_P || diag[i] >= GL_P) return false;
-        all[360 + i] = circ[i]; all[372 + i] = diag[i];
-        sum += circ[i];
-        if (diag[i] > maxdiag) maxdiag = diag[i];
-        if (circ[i] >> 24 || diag[i] >> 24) small = false;
-    }
-    if (sum + maxdiag >= ((unsigned __int128)1 << 24)) small = false;
-    init_hasher(all, small, h, ch);
-    return true;
-}
-
-// sum_idx alpha_t^idx * C_idx at zeta for challenge t (the constraint list of plonk_kernels.cuh / DESIGN.md §3.6), extension field
-gl_ext2 constraint_sum(u32 t, gl_ext2 x, gl_ext2 xn, u64 n, u32 R, bool poseidon, bool sha, const gl_ext2* q_ext, const u64* pos_consts, const std::vector<u64>& ks, const u64* beta,
-                       const u64* gamma, const u64* alpha, const gl_ext2* consts, const gl_ext2* sigmas, const gl_ext2* wires, const gl_ext2* zs,
-                       const gl_ext2* z_next, gl_ext2 pi_at_x) {
-    typedef GlpGateExt O;
-    const u32 M = R / CHUNK;
-    const gl_ext2 one{1, 0};
-    // L_1(x) = (x^n - 1) / (n (x - 1))
-    const gl_ext2 l1 = gl_ext_mul(gl_ext_sub(xn, one), ext_inv(gl_ext_scale(gl_ext_sub(x, one), n % GL_P)));
-    const gl_ext2 q = consts[0], c0 = consts[1], c1 = consts[2], c2 = consts[3], q_pi = consts[4], q_pos = consts[5];
-    gl_ext2 acc = gl_ext_mul(l1, gl_ext_sub(zs[t * M], one));
-    u64 ap = alpha[t];
-    acc = gl_ext_add(acc, gl_ext_scale(gl_ext_sub(gl_ext_mul(q_pi, wires[0]), pi_at_x), ap));       // public inputs, alpha^1
-    gl_ext2 prev = zs[t * M];
-    const gl_ext2 bx = gl_ext_scale(x, beta[t]);
-    for (u32 cidx = 0; cidx < M; cidx++) {
-        gl_ext2 num = one, den = one;
-        for (u32 j = cidx * CHUNK; j < (cidx + 1) * CHUNK; j++) {
-            const gl_ext2 wg = gl_ext_add(wires[j], gl_ext2{gamma[t], 0});
-            num = gl_ext_mul(num, gl_ext_add(wg, gl_ext_scale(bx, ks[j])));
-            den = gl_ext_mul(den, gl_ext_add(wg, gl_ext_scale(sigmas[j], beta[t])));
-        }
-        const gl_ext2 nx = cidx + 1 < M ? zs[t * M + 1 + cidx] : z_next[t];
-        const gl_ext2 perm = gl_ext_sub(gl_ext_mul(prev, num), gl_ext_mul(nx, den));
-        const gl_ext2* w8 = wires + cidx * CHUNK;
-        gl_ext2 g0 = gl_ext_mul(q, glp_arith_gate<O>(c0, c1, c2, w8[0], w8[1], w8[2], w8[3]));
-        gl_ext2 g1 = gl_ext_mul(q, glp_arith_gate<O>(c0, c1, c2, w8[4], w8[5], w8[6], w8[7]));
-        if (q_ext) {
-            const gl_ext2 ww[8] = {w8[0], w8[1], w8[2], w8[3], w8[4], w8[5], w8[6], w8[7]};
-            gl_ext2 e0, e1;
-            glp_ext_gate<O>(ww, e0, e1);
-            g0 = gl_ext_add(g0, gl_ext_mul(*q_ext, e0));
-            g1 = gl_ext_add(g1, gl_ext_mul(*q_ext, e1));
-        }
-        const gl_ext2 cons[3] = {perm, g0, g1};
-        for (int i = 0; i < 3; i++) {
-            ap = gl_mul(ap, alpha[t]);
-            acc = gl_ext_add(acc, gl_ext_scale(cons[i], ap));
-        }
-        prev = nx;
-    }
-    if (poseidon) {
-        gl_ext2 pacc{0, 0};
-        glp_poseidon_gate_constraints<O>([&](int j) -> gl_ext2 { return wires[j]; }, pos_consts, pos_consts + 360, pos_consts + 372,
-                                         [&](gl_ext2 con) {
-                                             ap = gl_mul(ap, alpha[t]);
-                                             pacc = gl_ext_add(pacc, gl_ext_scale(con, ap));
-                                         });
-        acc = gl_ext_add(acc, gl_ext_mul(q_pos, pacc));
-    }
-    if (sha) {                                   // consts then has GLP_PLONK_NCONST_SHA entries; the constraints arrive selector-weighted
-        const gl_ext2 qs[4] = {consts[6], consts[7], consts[8], consts[9]};
-        glp_sha_gate_constraints<O>([&](int j) -> gl_ext2 { return wires[j]; }, qs, c2, [&](gl_ext2 con) {
-            ap = gl_mul(ap, alpha[t]);
-            acc = gl_ext_add(acc, gl_ext_scale(con, ap));
-        });
-    }
-    return acc;
-}
-
-// PI(x) = sum_i pi_i * L_i(x),  L_i(x) = w^i (x^n - 1) / (n (x - w^i))   (the polynomial that is pi_i on row i < n_public, 0 elsewhere)
-gl_ext2 public_input_poly_at(const u64* pub, u64 n_pub, gl_ext2 x, gl_ext2 xn, u32 log_n) {
-    if (n_pub == 0) return gl_ext2{0, 0};
-    const u64 n = 1ull << log_n, w = gl_root_of_unity(log_n);
-    const gl_ext2 zh_over_n = gl_ext_scale(gl_ext_sub(xn, gl_ext2{1, 0}), gl_inv(n % GL_P));
-    gl_ext2 acc{0, 0};
-    u64 wi = 1;
-    for (u64 i = 0; i < n_pub; i++) {
-        const gl_ext2 li = gl_ext_mul(gl_ext_scale(zh_over_n, wi), ext_inv(gl_ext_sub(x, gl_ext2{wi, 0})));
-        acc = gl_ext_add(acc, gl_ext_scale(li, pub[i]));
-        wi = gl_mul(wi, w);
-    }
-    return acc;
-}
-}  // namespace
-
-static bool proof_args_ok(const uint8_t* proof, size_t len) { return proof && len && len % 8 == 0 && ((uintptr_t)proof & 7) == 0; }
-
-static int fri_verify_entry(Reject rj, const Hasher& h, glp_challenger& ch, const uint8_t* proof, size_t len, uint32_t min_queries,
-                            uint32_t min_pow_bits, uint32_t min_rate_bits, glp_fri_statement* st) {
-    Reader rd{(const u64*)proof, len / 8, 0};
-    FriInfo fi;
-    if (st) memset(st, 0, sizeof(*st));
-    int rc = fri_verify(rj, h, ch, rd, false, min_queries, min_pow_bits, min_rate_bits, fi);
-    if (rc == GLP_OK && st) {     // WHAT was proven: the caller compares it with the statement it expects
-        st->log_n = fi.log_n; st->rate_bits = fi.rb; st->cap_height = fi.cap0; st->n_batches = fi.nb; st->n_points = fi.n_pts;
-        st->num_queries = fi.nq; st->pow_bits = fi.pow_bits; st->shift = fi.shift;
-        st->zeta[0] = fi.zeta.a; st->zeta[1] = fi.zeta.b;
-        for (u32 p = 0; p < 4; p++) st->point_mult[p] = fi.mults[p];
-        st->caps_word_off = fi.caps_off; st->cap_words = (size_t)4 << fi.cap0;
-        st->openings_word_off = fi.openings_off; st->n_openings = fi.openings.size();
-        u32 np = 0;
-        for (u32 b = 0; b < fi.nb && b < 64; b++) { st->n_polys[b] = (u32)fi.n_polys[b]; st->open_mask[b] = (u32)fi.masks[b]; np += (u32)fi.n_polys[b]; }
-        st->total_polys = np;
-    }
+// the single verifiers' reason goes to the ctx's error text, as "proof rejected: <reason>"
+int to_ctx(glp_ctx* c, int rc, const char* text) {
+    if (rc == GLP_E_REJECT) glp_set_err(c, "%s", text);
     return rc;
 }
 
-static int plonk_verify_entry(Reject rj, const Hasher& h, glp_challenger& ch, const uint8_t* proof, size_t len, const uint64_t* h_circuit_cap,
-                              size_t cap_words, const uint64_t* h_public, size_t n_public_expected, uint32_t min_queries, uint32_t min_pow_bits) {
-    Reader rd{(const u64*)proof, len / 8, 0};
-    auto take_obs = [&](size_t k, const u64** out) -> bool {
-        if (!rd.take(k, out)) return false;
-        for (size_t i = 0; i < k; i++) ch.observe((*out)[i] % GL_P);
-        return true;
-    };
-    const u64* hd;
-    if (!take_obs(8, &hd)) return rj.fail("truncated");
-    const u64 tag = hd[0], log_n = hd[1], W = hd[2], R = hd[3], rb = hd[4], cap_h = hd[5], n_pub = hd[6], flags = hd[7];
-    if (tag != PLONK_TAG || rb != 3 || W % 8 || W < 8 || W > 160 || R % 8 || R < 8 || R > W || log_n < 3 || log_n > 24 ||
-        n_pub > (1ull << log_n) || (flags & ~(u64)(GLP_CIRCUIT_POSEIDON_GATE | GLP_CIRCUIT_SHA_GATES | GLP_CIRCUIT_EXT_GATE)))
-        return rj.fail("bad plonk header");
-    const bool poseidon = (flags & GLP_CIRCUIT_POSEIDON_GATE) != 0, sha = (flags & GLP_CIRCUIT_SHA_GATES) != 0;
-    if (poseidon && (W < GLP_POS_GATE_WIRES || R < 24)) return rj.fail("bad plonk header");
-    if (sha && (W < GLP_SHA_GATE_WIRES || R < 16)) return rj.fail("bad plonk header");
-    const u64 n_const = (u64)glp_plonk_n_const((u32)flags);
-    const u64 n = 1ull << log_n;
-    const u32 log_N = (u32)(log_n + rb), M = (u32)(R / CHUNK);
-    const u64* pub;
-    if (!rd.take((size_t)n_pub, &pub)) return rj.fail("truncated");
-    for (u64 i = 0; i < n_pub; i++) {
-        if (pub[i] >= GL_P) return rj.fail("non-canonical public input");
-        ch.observe(pub[i]);
+// ---- the batched verifiers ---------------------------------------------------------------------------------------------------------
+typedef GlpPoolBuf DBuf;
+#define GLP_VB_CHUNK_ITEMS (1ull << 30)
+
+// the device phase of one chunk's plan: one staging block up (descriptors | tables | items | tree table | keys | proof words), two launches,
+// the keys back, one synchronise.  `up` (the staging block) and `keys` belong to the CALLER's frame: the asynchronous copies read and write them,
+// and on an error return the caller synchronises the stream before either goes away.
+int device_phase(glp_ctx* c, const VerifyPlan& P, const std::vector<const u64*>& words, std::vector<u64>& up, std::vector<unsigned long long>& keys,
+                 u32* counts) {
+    const size_t nd = P.desc.size();
+    keys.assign(nd, GLP_VB_KEY_NONE);
+    if (nd == 0 || P.arith.empty()) return GLP_OK;
+    std::vector<u64> items;
+    std::vector<u32> tree_first;
+    flatten_items(P, items, tree_first);
+    const size_t n_merkle = items.size(), n_arith = P.arith.size();
+    for (auto& it : P.arith) items.push_back((u64)it.desc | ((u64)it.q << 32));
+    const size_t w_desc = nd * (sizeof(GlpVerifyDesc) / 8), w_aux = P.aux.size(), w_items = items.size(), w_tree = (tree_first.size() + 1) / 2, w_keys = nd;
+    const size_t o_aux = w_desc, o_items = o_aux + w_aux, o_tree = o_items + w_items, o_keys = o_tree + w_tree, o_slab = o_keys + w_keys;
+    up.assign(o_slab + P.slab_words, 0);
+    memcpy(up.data(), P.desc.data(), w_desc * 8);
+    if (w_aux) memcpy(up.data() + o_aux, P.aux.data(), w_aux * 8);
+    memcpy(up.data() + o_items, items.data(), w_items * 8);
+    memcpy(up.data() + o_tree, tree_first.data(), tree_first.size() * 4);
+    for (size_t k = 0; k < nd; k++) up[o_keys + k] = GLP_VB_KEY_NONE;
+    for (size_t k = 0; k < nd; k++) {
+        const size_t used = (k + 1 < nd ? P.desc[k + 1].base : P.slab_words) - P.desc[k].base;
+        memcpy(up.data() + o_slab + P.desc[k].base, words[k], used * 8);
     }
-    // the proof must be about THIS statement: the caller's public inputs, word for word
-    if (h_public && (n_public_expected != n_pub || memcmp(h_public, pub, (size_t)n_pub * 8) != 0)) return rj.fail("public inputs differ from the expected statement");
-    const size_t capw = (size_t)4 << (cap_h < log_N ? cap_h : log_N);
-    const u64 *cap_pre, *cap_wires, *cap_zs, *cap_q;
-    if (cap_h > 32 || !take_obs(capw, &cap_pre) || !take_obs(capw, &cap_wires)) return rj.fail("truncated");
-    // ... and about THIS circuit: its preprocessed commitment is the verifying key
-    if (h_circuit_cap && (cap_words != capw || memcmp(h_circuit_cap, cap_pre, capw * 8) != 0)) return rj.fail("preprocessed commitment differs from the circuit's");
-    u64 beta[NCHAL], gamma[NCHAL], alpha[NCHAL];
-    for (u32 t = 0; t < NCHAL; t++) beta[t] = ch.challenge();
-    for (u32 t = 0; t < NCHAL; t++) gamma[t] = ch.challenge();
-    if (!take_obs(capw, &cap_zs)) return rj.fail("truncated");
-    for (u32 t = 0; t < NCHAL; t++) alpha[t] = ch.challenge();
-    if (!take_obs(capw, &cap_q)) return rj.fail("truncated");
-    FriInfo fi;
-    int rc = fri_verify(rj, h, ch, rd, false, min_queries, min_pow_bits, 1, fi);
-    if (rc != GLP_OK) return rc;
-    // the FRI part must be about exactly these commitments, shapes and points
-    const u64 want_polys[4] = {n_const + R, W, (u64)NCHAL * M, (u64)NCHAL << rb};
-    if (fi.nb != 4 || fi.log_n != log_n || fi.rb != rb || fi.cap0 != (cap_h < log_N ? cap_h : log_N)) return rj.fail("FRI statement does not match the circuit shape");
-    const u64* want_caps[4] = {cap_pre, cap_wires, cap_zs, cap_q};
-    for (int b = 0; b < 4; b++) {
-        if (fi.n_polys[b] != want_polys[b]) return rj.fail("FRI statement does not match the circuit shape");
-        if (memcmp(fi.caps[b], want_caps[b], capw * 8) != 0) return rj.fail("FRI caps differ from the committed caps");
+    DBuf d_up(c);
+    if (d_up.alloc(up.size() * 8) != hipSuccess) return GLP_E_NOMEM;
+    GLP_HIPCHK(c, hipMemcpyAsync(d_up.p, up.data(), up.size() * 8, hipMemcpyHostToDevice, c->stream));
+    GlpVerifyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.desc = reinterpret_cast<const GlpVerifyDesc*>(d_up.u());
+    a.aux = d_up.u() + o_aux; a.items = d_up.u() + o_items; a.tree_first = reinterpret_cast<const u32*>(d_up.u() + o_tree);
+    a.keys = reinterpret_cast<unsigned long long*>(d_up.u() + o_keys); a.slab = d_up.u() + o_slab;
+    a.n_trees = (u32)P.by_tree.size(); a.n_items = n_merkle;
+    a.k = glp_dev_consts(c->hash);
+    const bool small = c->hash->small_mds && !getenv("GLP_K7_GENERIC_MDS");
+    if (n_merkle) {
+        const dim3 g((unsigned)((n_merkle + GLP_VB_BLOCK - 1) / GLP_VB_BLOCK)), blk(GLP_VB_BLOCK);
+        if (small) hipLaunchKernelGGL(glp_verify_merkle_kernel<true>, g, blk, 0, c->stream, a);
+        else hipLaunchKernelGGL(glp_verify_merkle_kernel<false>, g, blk, 0, c->stream, a);
+        GLP_HIPCHK(c, hipGetLastError());
+        counts[0]++;
     }
-    const u64 g = gl_root_of_unity((unsigned)log_n);
-    if (fi.n_pts != 2 || !ext_eq(fi.points[0], fi.zeta) || !ext_eq(fi.points[1], gl_ext_scale(fi.zeta, g))) return rj.fail("wrong opening points");
-    const std::pair<u32, u32> want_order[5] = {{0, 0}, {0, 1}, {0, 2}, {0, 3}, {1, 2}};
-    if (fi.order.size() != 5) return rj.fail("wrong opening points");
-    for (int i = 0; i < 5; i++)
-        if (fi.order[i] != want_order[i]) return rj.fail("wrong opening points");
-    const gl_ext2* pre = fi.openings.data() + fi.open_off[0];
-    const gl_ext2* wires = fi.openings.data() + fi.open_off[1];
-    const gl_ext2* zs = fi.openings.data() + fi.open_off[2];
-    const gl_ext2* quot = fi.openings.data() + fi.open_off[3];
-    const gl_ext2* zs_next = fi.openings.data() + fi.open_off[4];
-    std::vector<u64> ks(R);
-    {
-        u64 t = 1;
-        for (u64 j = 0; j < R; j++) { ks[j] = t; t = gl_mul(t, 7); }
-    }
-    gl_ext2 zn = fi.zeta;
-    for (u64 i = 0; i < log_n; i++) zn = gl_ext_mul(zn, zn);
-    const gl_ext2 zh = gl_ext_sub(zn, gl_ext2{1, 0});
-    const gl_ext2 pi_z = public_input_poly_at(pub, n_pub, fi.zeta, zn, (u32)log_n);
-    gl_ext2 z_next[NCHAL];
-    for (u32 t = 0; t < NCHAL; t++) z_next[t] = zs_next[t * M];
-    for (u32 t = 0; t < NCHAL; t++) {
-        const gl_ext2 lhs = constraint_sum(t, fi.zeta, zn, n, (u32)R, poseidon, sha, (flags & GLP_CIRCUIT_EXT_GATE) ? pre + n_const - 1 : nullptr, h.consts.data(), ks, beta, gamma, alpha, pre,
-                                           pre + n_const,
-                                           wires, zs, z_next, pi_z);
-        gl_ext2 tz{0, 0}, zp{1, 0};
-        for (u32 cc = 0; cc < (1u << rb); cc++) {
-            tz = gl_ext_add(tz, gl_ext_mul(zp, quot[t * (1u << rb) + cc]));
-            zp = gl_ext_mul(zp, zn);
+    a.items = d_up.u() + o_items + n_merkle; a.n_items = n_arith;
+    hipLaunchKernelGGL(glp_verify_arith_kernel<0>, dim3((unsigned)((n_arith + GLP_VB_BLOCK - 1) / GLP_VB_BLOCK)), dim3(GLP_VB_BLOCK), 0, c->stream, a);
+    GLP_HIPCHK(c, hipGetLastError());
+    counts[0]++;
+    GLP_HIPCHK(c, hipMemcpyAsync(keys.data(), a.keys, nd * 8, hipMemcpyDeviceToHost, c->stream));
+    GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+    counts[1]++;
+    return GLP_OK;
+}
+
+// c == nullptr: the ctx-less form (items on the host, constants in h0)
+int verify_batch(glp_ctx* c, const Hasher& h0, const BatchArgs& A, u32* out_counts) {
+    std::vector<ProofState> S(A.B);
+    glp_challenger ch;                           // one transcript object for the call, reset per proof
+    ch.consts = h0.consts; ch.small_mds = h0.small_mds;
+    u32 counts[4] = {0, 0, 0, 0};
+    int rc = GLP_OK;
+    for (u32 i0 = 0; i0 < A.B && rc == GLP_OK;) {
+        // a chunk: proofs from i0 while their Merkle items stay below the limit of one launch
+        VerifyPlan P;
+        std::vector<const u64*> words;
+        u32 i1 = i0;
+        while (i1 < A.B && (i1 == i0 || P.n_merkle() < GLP_VB_CHUNK_ITEMS)) {
+            const size_t nd = P.desc.size();
+            host_phase(A, h0, ch, i1, i1 + 1, S, P);
+            if (P.desc.size() > nd) words.push_back((const u64*)A.proofs[i1]);
+            i1++;
         }
-        if (!ext_eq(lhs, gl_ext_mul(zh, tz))) return rj.fail("PLONK identity fails at zeta");
+        std::vector<unsigned long long> keys(P.desc.size(), GLP_VB_KEY_NONE);
+        std::vector<u64> up;                     // the chunk's staging block: lives until the stream has been synchronised
+        if (c) {
+            rc = device_phase(c, P, words, up, keys, counts);
+            if (rc) (void)hipStreamSynchronize(c->stream);     // copies in flight read `up` and write `keys`, both of this frame (not counted: not on the path of a verdict)
+        } else
+            glp_vb_run_host(P, words.data(), h0.k(), h0.small_mds, keys.data());
+        if (rc == GLP_OK) {
+            // descriptors are numbered per chunk: settle with the chunk's keys
+            settle(A, S, keys.data(), i0, i1, &counts[2], &counts[3]);
+        }
+        i0 = i1;
+    }
+    for (int k = 0; k < 4; k++) out_counts[k] = counts[k];
+    return rc;
+}
+
+int first_refused(const BatchArgs& A) {
+    for (u32 i = 0; i < A.B; i++)
+        if (A.verdicts[i].status != GLP_OK) return (int)i;
+    return -1;
+}
+
+int batch_entry(glp_ctx* c, const BatchArgs& A, const char* who) {
+    for (int k = 0; k < 4; k++) c->verify_batch_counts[k] = 0;
+    if (A.B == 0) return GLP_OK;
+    if (const char* bad = batch_args_bad(A)) { glp_set_err(c, "%s: bad argument (%s)", who, bad); return GLP_E_INVALID; }
+    Hasher h;
+    glp_challenger ch;
+    if (!make_hasher(c, h, ch)) return GLP_E_STATE;
+    const int rc = verify_batch(c, h, A, c->verify_batch_counts);
+    if (rc != GLP_OK) return rc;
+    const int bad = first_refused(A);
+    if (bad >= 0) {
+        const glp_verify_verdict& v = A.verdicts[bad];
+        if (v.query != 0xFFFFFFFFu) glp_set_err(c, "%s: proof %d rejected: %s (query %u)", who, bad, glp_vr_text(v.reason), v.query);
+        else glp_set_err(c, "%s: proof %d rejected: %s", who, bad, glp_vr_text(v.reason));
     }
     return GLP_OK;
+}
+}  // namespace
+
+extern "C" int glp_plonk_verify_batch(glp_ctx* c, const uint8_t* const* h_proofs, const size_t* lens, uint32_t B, const uint64_t* h_circuit_cap,
+                                      size_t cap_words, const uint64_t* h_public, size_t n_public, uint32_t min_queries, uint32_t min_pow_bits,
+                                      glp_verify_verdict* h_verdicts, uint64_t* h_digests) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    const BatchArgs A{true, h_proofs, lens, B, h_circuit_cap, cap_words, h_public, n_public, min_queries, min_pow_bits, 1, h_verdicts, h_digests, nullptr};
+    return batch_entry(c, A, "glp_plonk_verify_batch");
+}
+extern "C" int glp_fri_verify_batch(glp_ctx* c, const uint8_t* const* h_proofs, const size_t* lens, uint32_t B, uint32_t min_queries,
+                                    uint32_t min_pow_bits, uint32_t min_rate_bits, glp_verify_verdict* h_verdicts, glp_fri_statement* statements) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    const BatchArgs A{false, h_proofs, lens, B, nullptr, 0, nullptr, 0, min_queries, min_pow_bits, min_rate_bits, h_verdicts, nullptr, statements};
+    return batch_entry(c, A, "glp_fri_verify_batch");
+}
+extern "C" const char* glp_verify_reason_text(uint32_t reason) { return glp_vr_text(reason); }
+extern "C" int glp_verify_last_batch_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs, uint32_t* n_on_device, uint32_t* n_fallback) {
+    if (!c) return GLP_E_INVALID;
+    if (n_launches) *n_launches = c->verify_batch_counts[0];
+    if (n_host_syncs) *n_host_syncs = c->verify_batch_counts[1];
+    if (n_on_device) *n_on_device = c->verify_batch_counts[2];
+    if (n_fallback) *n_fallback = c->verify_batch_counts[3];
+    return GLP_OK;
+}
+static int batch_host_entry(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const BatchArgs& A, uint32_t* n_on_device,
+                            uint32_t* n_fallback) {
+    if (n_on_device) *n_on_device = 0;
+    if (n_fallback) *n_fallback = 0;
+    Hasher h;
+    glp_challenger ch;
+    if (!make_hasher_from(h_rc, h_mds_circ, h_mds_diag, h, ch)) return GLP_E_INVALID;
+    if (A.B == 0) return GLP_OK;
+    if (batch_args_bad(A)) return GLP_E_INVALID;
+    u32 counts[4];
+    const int rc = verify_batch(nullptr, h, A, counts);
+    if (n_on_device) *n_on_device = counts[2];
+    if (n_fallback) *n_fallback = counts[3];
+    return rc;
+}
+extern "C" int glp_plonk_verify_batch_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* const* h_proofs,
+                                           const size_t* lens, uint32_t B, const uint64_t* h_circuit_cap, size_t cap_words, const uint64_t* h_public,
+                                           size_t n_public, uint32_t min_queries, uint32_t min_pow_bits, glp_verify_verdict* h_verdicts,
+                                           uint64_t* h_digests, uint32_t* n_on_device, uint32_t* n_fallback) {
+    const BatchArgs A{true, h_proofs, lens, B, h_circuit_cap, cap_words, h_public, n_public, min_queries, min_pow_bits, 1, h_verdicts, h_digests, nullptr};
+    return batch_host_entry(h_rc, h_mds_circ, h_mds_diag, A, n_on_device, n_fallback);
+}
+extern "C" int glp_fri_verify_batch_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* const* h_proofs,
+                                         const size_t* lens, uint32_t B, uint32_t min_queries, uint32_t min_pow_bits, uint32_t min_rate_bits,
+                                         glp_verify_verdict* h_verdicts, glp_fri_statement* statements, uint32_t* n_on_device, uint32_t* n_fallback) {
+    const BatchArgs A{false, h_proofs, lens, B, nullptr, 0, nullptr, 0, min_queries, min_pow_bits, min_rate_bits, h_verdicts, nullptr, statements};
+    return batch_host_entry(h_rc, h_mds_circ, h_mds_diag, A, n_on_device, n_fallback);
 }
 
 extern "C" int glp_fri_verify_ex(glp_ctx* c, const uint8_t* proof, size_t len, uint32_t min_queries, uint32_t min_pow_bits,
@@ -550,7 +220,9 @@ extern "C" int glp_fri_verify_ex(glp_ctx* c, const uint8_t* proof, size_t len, u
     Hasher h;
     glp_challenger ch;
     if (!make_hasher(c, h, ch)) return GLP_E_STATE;
-    return fri_verify_entry(Reject{c, nullptr, 0}, h, ch, proof, len, min_queries, min_pow_bits, min_rate_bits, statement);
+    char text[160];
+    Reject rj{text, sizeof(text)};
+    return to_ctx(c, fri_verify_entry(rj, h, ch, proof, len, min_queries, min_pow_bits, min_rate_bits, statement), text);
 }
 extern "C" int glp_fri_verify(glp_ctx* c, const uint8_t* proof, size_t len, uint32_t min_queries, uint32_t min_pow_bits) {
     return glp_fri_verify_ex(c, proof, len, min_queries, min_pow_bits, 1, nullptr);
@@ -563,29 +235,13 @@ extern "C" int glp_plonk_verify_ex(glp_ctx* c, const uint8_t* proof, size_t len,
     Hasher h;
     glp_challenger ch;
     if (!make_hasher(c, h, ch)) return GLP_E_STATE;
-    return plonk_verify_entry(Reject{c, nullptr, 0}, h, ch, proof, len, h_circuit_cap, cap_words, h_public, n_public, min_queries, min_pow_bits);
+    char text[160];
+    Reject rj{text, sizeof(text)};
+    return to_ctx(c, plonk_verify_entry(rj, h, ch, proof, len, h_circuit_cap, cap_words, h_public, n_public, min_queries, min_pow_bits), text);
 }
 extern "C" int glp_plonk_verify(glp_ctx* c, const uint8_t* proof, size_t len, const uint64_t* h_circuit_cap, size_t cap_words,
                                 uint32_t min_queries, uint32_t min_pow_bits) {
     return glp_plonk_verify_ex(c, proof, len, h_circuit_cap, cap_words, nullptr, 0, min_queries, min_pow_bits);
-}
-// digest of a circuit proof's STATEMENT AND COMMITMENTS: hash_no_pad(header (8) || public inputs || the four caps).  The caps bind every
-// committed polynomial, so two proofs with equal digests are proofs about the same circuit, inputs and witness commitment; this is the
-// leaf value of the Reduce step's aggregation tree (recursion.py).  No verification.
-static int proof_digest(const Hasher& h, const uint8_t* proof, size_t len, uint64_t* out4) {
-    const u64* w = (const u64*)proof;
-    const size_t nw = len / 8;
-    if (nw < 8 || w[0] != PLONK_TAG || w[1] > 24 || w[4] != 3 || w[5] > 12 || w[6] > (1ull << 24)) return GLP_E_INVALID;
-    const u32 log_N = (u32)(w[1] + w[4]);
-    const size_t capw = (size_t)4 << (w[5] < log_N ? w[5] : log_N);
-    const size_t total = 8 + (size_t)w[6] + 4 * capw;
-    if (total > nw) return GLP_E_INVALID;
-    std::vector<u64> buf(total);
-    for (size_t i = 0; i < total; i++) buf[i] = w[i] % GL_P;
-    u64 d[4];
-    h.hash_or_noop(buf.data(), total, d);
-    memcpy(out4, d, 32);
-    return GLP_OK;
 }
 extern "C" int glp_plonk_proof_digest(glp_ctx* c, const uint8_t* proof, size_t len, uint64_t* h_out4) {
     if (!c) return GLP_E_INVALID;
@@ -874,7 +530,8 @@ extern "C" int glp_fri_verify_host_ex(const uint64_t* h_rc, const uint64_t* h_md
     Hasher h;
     glp_challenger ch;
     if (!proof_args_ok(proof, len) || !make_hasher_from(h_rc, h_mds_circ, h_mds_diag, h, ch)) return GLP_E_INVALID;
-    return fri_verify_entry(Reject{nullptr, err, err_len}, h, ch, proof, len, min_queries, min_pow_bits, min_rate_bits, statement);
+    Reject rj{err, err_len};
+    return fri_verify_entry(rj, h, ch, proof, len, min_queries, min_pow_bits, min_rate_bits, statement);
 }
 extern "C" int glp_fri_verify_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* proof, size_t len,
                                    uint32_t min_queries, uint32_t min_pow_bits, char* err, size_t err_len) {
@@ -887,7 +544,8 @@ extern "C" int glp_plonk_verify_host_ex(const uint64_t* h_rc, const uint64_t* h_
     Hasher h;
     glp_challenger ch;
     if (!proof_args_ok(proof, len) || !make_hasher_from(h_rc, h_mds_circ, h_mds_diag, h, ch)) return GLP_E_INVALID;
-    return plonk_verify_entry(Reject{nullptr, err, err_len}, h, ch, proof, len, h_circuit_cap, cap_words, h_public, n_public, min_queries, min_pow_bits);
+    Reject rj{err, err_len};
+    return plonk_verify_entry(rj, h, ch, proof, len, h_circuit_cap, cap_words, h_public, n_public, min_queries, min_pow_bits);
 }
 extern "C" int glp_plonk_verify_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* proof, size_t len,
                                      const uint64_t* h_circuit_cap, size_t cap_words, uint32_t min_queries, uint32_t min_pow_bits, char* err,

@@ -141,16 +141,49 @@ def _prove_local(prove_leaf, ids):
             return sorted((p for f in futs for p in f.result()), key=lambda t: t[0])
 
 
-def reduce_verify(verify_leaf, proofs, device=None, comm=None):
-    """The Reduce step in its NATIVE form (the recursive forms are reduce_recursive / reduce_tree / reduce_tree_distributed): every gathered leaf
-    proof is checked by the native verifier (``verify_leaf(proof_bytes) -> bool``, e.g. ``PlonkCircuit.verify``, or a list of them — one per
-    ctx — run by one host thread each), the work split across
-    ranks — rank r checks the leaves PROVED BY rank r+1 — and the verdicts are combined with one
-    all-reduce(MIN).  The result is a boolean ("all leaves verify"), not a succinct proof: that is what the recursive forms produce."""
+def _verdict(row):
+    """one entry of what a ``verify_batch`` callable returned: a real boolean, or a row ``(ok, reason, query)`` as ``PlonkCircuit.verify_batch``
+    gives it.  Anything else is refused — truthiness is not a verdict (a non-empty tuple is truthy whatever it says)."""
+    import numpy as np
+    if isinstance(row, (tuple, list)) and len(row) == 3:
+        row = row[0]
+    if isinstance(row, (bool, np.bool_)):
+        return bool(row)
+    raise TypeError(f"verify_batch must return booleans or (ok, reason, query) rows, got {row!r}")
+
+
+def _verify_share(verify_batch, proofs, ids):
+    """this rank's share through ONE batched call: (all accepted, {leaf index: digest} of the ACCEPTED leaves when the callable also returned
+    digests).  The callable returns the verdicts, or the pair (verdicts, digests) — told apart by the second member being the digest list."""
+    res = verify_batch([proofs[i] for i in ids]) if ids else []
+    digests = None
+    if isinstance(res, tuple) and len(res) == 2 and isinstance(res[0], list):
+        res, digests = res
+    res = list(res)
+    if len(res) != len(ids) or (digests is not None and len(digests) != len(ids)):
+        raise ValueError(f"verify_batch returned {len(res)} verdicts for {len(ids)} proofs")
+    oks = [_verdict(r) for r in res]
+    have = {}
+    if digests is not None:
+        for i, ok, d in zip(ids, oks, digests):
+            if ok and d is not None:                      # a refused or malformed leaf has no digest to keep (None: its header does not parse)
+                have[i] = [int(v) for v in d]
+    return all(oks), have
+
+
+def _reduce_verify(verify_leaf, proofs, device, comm, verify_batch):
+    """(every leaf verifies, {leaf index: digest} that a ``verify_batch`` callable handed over for this rank's share)"""
     rank, world = _world(comm)
     owner = (rank + 1) % world
     ids = list(range(owner, len(proofs), world))
-    if callable(verify_leaf):
+    have, failure = {}, None
+    if verify_batch is not None:
+        try:
+            all_ok, have = _verify_share(verify_batch, proofs, ids)
+        except (TypeError, ValueError) as e:              # an unusable return value: this rank still joins the all-reduce, then raises
+            all_ok, failure = False, e
+        ok = int(all_ok)
+    elif callable(verify_leaf):
         ok = int(all([verify_leaf(proofs[i]) for i in ids]))
     else:
         # a list of verifiers (one ctx each): host threads, the native verifier runs without the GIL
@@ -166,25 +199,42 @@ def reduce_verify(verify_leaf, proofs, device=None, comm=None):
             t = torch.tensor([ok], dtype=torch.int32, device=device if device is not None else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             ok = int(t.item())
-    return bool(ok)
+    if failure is not None:
+        raise failure
+    return bool(ok), have
+
+
+def reduce_verify(verify_leaf, proofs, device=None, comm=None, verify_batch=None):
+    """The Reduce step in its NATIVE form (the recursive forms are reduce_recursive / reduce_tree / reduce_tree_distributed): every gathered leaf
+    proof is checked by the native verifier (``verify_leaf(proof_bytes) -> bool``, e.g. ``PlonkCircuit.verify``, or a list of them — one per
+    ctx — run by one host thread each), the work split across
+    ranks — rank r checks the leaves PROVED BY rank r+1 — and the verdicts are combined with one
+    all-reduce(MIN).  The result is a boolean ("all leaves verify"), not a succinct proof: that is what the recursive forms produce.
+    ``verify_batch`` (opt-in; ``list[bytes] -> list[bool]``): the rank's share goes through it in one call and ``verify_leaf`` is not used.
+    The entries must be real booleans or the ``(ok, reason, query)`` rows of ``PlonkCircuit.verify_batch`` (so ``ck.verify_batch`` itself is a
+    valid callable); anything else raises ``TypeError``.  It may return ``(verdicts, digests)`` — ``verify_batch(..., want_digests=True)`` —
+    to hand the accepted leaves' digests to ``reduce_aggregate``; a ``None`` digest (a leaf whose header does not parse) is skipped."""
+    return _reduce_verify(verify_leaf, proofs, device, comm, verify_batch)[0]
 
 
 ZERO_DIGEST = [0, 0, 0, 0]      # pads the leaf list to a power of two in the aggregation tree
 
 
-def reduce_aggregate(prover, verify_leaf, proofs, device=None, comm=None, num_queries=28, pow_bits=16):
+def reduce_aggregate(prover, verify_leaf, proofs, device=None, comm=None, num_queries=28, pow_bits=16, verify_batch=None):
     """The Reduce step with its first in-circuit part (recursion.py).  (1) every gathered leaf proof is verified natively, split
     across ranks, verdicts all-reduced (``reduce_verify``: host arithmetic — the part that is NOT in-circuit yet);
     (2) rank 0 hashes each leaf proof to its 4-word digest (statement + commitments) and PROVES, on the GPU, the binary Poseidon
     tree over the digests: one succinct proof whose public inputs are the digests and the root.  Returns a dict: ``ok`` (every leaf
-    verifies), and on rank 0 ``root_proof``, ``root``, ``digests``, ``key`` (the aggregation circuit's verifying key)."""
+    verifies), and on rank 0 ``root_proof``, ``root``, ``digests``, ``key`` (the aggregation circuit's verifying key).
+    ``verify_batch`` as in ``reduce_verify``; the digests it returns for this rank's share are used as they are, the others are computed
+    one by one as before."""
     import importlib
     rank, _ = _world(comm)
-    ok = reduce_verify(verify_leaf, proofs, device=device, comm=comm)
+    ok, have = _reduce_verify(verify_leaf, proofs, device, comm, verify_batch)
     out = {"ok": ok}
     if rank == 0 and ok:
         rec = importlib.import_module(__package__ + ".recursion")
-        digests = [prover.proof_digest(p) for p in proofs]
+        digests = [have[i] if i in have else prover.proof_digest(p) for i, p in enumerate(proofs)]
         size = 1 << max(1, (len(digests) - 1).bit_length())
         digests += [ZERO_DIGEST] * (size - len(digests))
         root_proof, root, key = rec.aggregate(prover, digests, num_queries, pow_bits)

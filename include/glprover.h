@@ -427,6 +427,89 @@ int glp_plonk_verify(glp_ctx* ctx, const uint8_t* h_proof, size_t proof_len, con
  * (circuit, public inputs): a verifier that passes NULL for either accepts proofs of OTHER statements. */
 int glp_plonk_verify_ex(glp_ctx* ctx, const uint8_t* h_proof, size_t proof_len, const uint64_t* h_circuit_cap, size_t cap_words,
                         const uint64_t* h_public, size_t n_public, uint32_t min_queries, uint32_t min_pow_bits);
+/* ---- batched verification: B proofs per call, the query phase on the device (opt-in; the single verifiers above are unchanged) ----
+ * Per proof the HOST runs what is serial: header and range checks, the binding to h_circuit_cap / h_public, the transcript replay, proof of
+ * work, the query indices, the alpha powers and opening sums and — after the queries, as the single verifier orders them — the trailing-data
+ * check, the shape checks and the PLONK identity at zeta.  The query loop, which is independent per (proof, query), runs on the DEVICE for all
+ * proofs of the call at once: one work-item per (proof, query, Merkle tree) — leaf canonicity, leaf hash, path walk, cap compare — and one per
+ * (proof, query) — combination at x, the folds, the final polynomial.  Every failure inside the loop has a key (query, step in the loop's
+ * order); the lowest key of a proof is the failure the single verifier stops at, so status, reason and query of every verdict EQUAL what
+ * glp_plonk_verify_ex / glp_fri_verify_ex give on the same bytes (reason: glp_verify_reason_text(reason) is exactly the text after
+ * "proof rejected: ").  A failure the host finds before the loop wins outright; one it finds after the loop counts only when no item failed.
+ * Tampered bytes: the items use no offset, length or index that the host phase has not derived from the range-checked header and checked
+ * against proof_len; the query index is the transcript's; a query that does not lie wholly inside the proof is settled on the host.
+ * A proof whose shape the items do not take (arity_bits > 4, more than 65536 opened values, 2^31 words or more) is verified inside the same
+ * call by the single verifier's code: on_device = 0, counted in n_fallback.
+ * h_proofs[i]: 8-byte aligned, lens[i] a non-zero multiple of 8; the same pointer may appear twice.  h_public: NULL = do not bind, else
+ * [B][n_public] expected public inputs.  h_digests (may be NULL): [B][4], what glp_plonk_proof_digest gives, zero where it would refuse.
+ * statements (may be NULL): [B], filled for accepted proofs as glp_fri_verify_ex does, zero otherwise.
+ * GLP_OK when the call ran (the verdicts are per proof; glp_last_error names the first refused proof and its reason); B == 0 is GLP_OK and
+ * does nothing; GLP_E_INVALID for a null or misaligned argument; GLP_E_STATE without Poseidon constants.
+ * Whatever B is (glp_verify_last_batch_counts): launches = 2 (Merkle items, arithmetic items) and synchronises = 1 per chunk, and one chunk
+ * holds up to 2^30 Merkle items (B * queries * (batches + layers)): 2 launches and 1 synchronise for every B a host can hold.  No launch and no
+ * synchronise when no proof reaches the query phase.  The count is of the driver's explicit stream synchronises.
+ * Transient device memory per chunk: 8 * (sum of the words before the end of each recorded proof's last query) + 8 * (sum over proofs of
+ * queries + 3 batches + 6 layers + 4 * 4 + 2 * opened values + order entries) + 120 * proofs + 8 * (Merkle items + arithmetic items) + 8 * proofs. */
+#define GLP_VR_NONE 0u
+#define GLP_VR_TRUNCATED 1u
+#define GLP_VR_BAD_TAG 2u
+#define GLP_VR_BAD_HEADER 3u
+#define GLP_VR_HEADER_RANGE 4u
+#define GLP_VR_RATE_ONE 5u
+#define GLP_VR_WEAK_PARAMS 6u
+#define GLP_VR_LOW_RATE 7u
+#define GLP_VR_OPEN_MASKS 8u
+#define GLP_VR_POINT_MULT 9u
+#define GLP_VR_CAP_HEIGHT 10u
+#define GLP_VR_CAP_NONCANONICAL 11u
+#define GLP_VR_OPENING_NONCANONICAL 12u
+#define GLP_VR_LAYER_CAP_NONCANONICAL 13u
+#define GLP_VR_FINAL_NONCANONICAL 14u
+#define GLP_VR_POW 15u
+#define GLP_VR_QUERY_INDEX 16u
+#define GLP_VR_LEAF_NONCANONICAL 17u
+#define GLP_VR_MERKLE_PATH 18u
+#define GLP_VR_QUERY_AT_POINT 19u
+#define GLP_VR_LAYER_LEAF_NONCANONICAL 20u
+#define GLP_VR_FOLD 21u
+#define GLP_VR_LAYER_MERKLE_PATH 22u
+#define GLP_VR_FINAL_POLY 23u
+#define GLP_VR_TRAILING 24u
+#define GLP_VR_PLONK_HEADER 25u
+#define GLP_VR_PUBLIC_NONCANONICAL 26u
+#define GLP_VR_PUBLIC_DIFFER 27u
+#define GLP_VR_CIRCUIT_DIFFER 28u
+#define GLP_VR_FRI_SHAPE 29u
+#define GLP_VR_FRI_CAPS 30u
+#define GLP_VR_POINTS 31u
+#define GLP_VR_IDENTITY 32u
+#define GLP_VR_COUNT 33u
+typedef struct {
+    int32_t status;      /* GLP_OK / GLP_E_REJECT */
+    uint32_t reason;     /* GLP_VR_*: index into the single verifier's reason texts */
+    uint32_t query;      /* failing query, 0xFFFFFFFF outside the query loop */
+    uint32_t on_device;  /* 1: the query phase of this proof ran as items of the batched phase */
+} glp_verify_verdict;
+int glp_plonk_verify_batch(glp_ctx* ctx, const uint8_t* const* h_proofs, const size_t* lens, uint32_t B, const uint64_t* h_circuit_cap,
+                           size_t cap_words, const uint64_t* h_public /* [B][n_public] or NULL */, size_t n_public, uint32_t min_queries,
+                           uint32_t min_pow_bits, glp_verify_verdict* h_verdicts, uint64_t* h_digests /* [B][4] or NULL */);
+int glp_fri_verify_batch(glp_ctx* ctx, const uint8_t* const* h_proofs, const size_t* lens, uint32_t B, uint32_t min_queries,
+                         uint32_t min_pow_bits, uint32_t min_rate_bits, glp_verify_verdict* h_verdicts,
+                         glp_fri_statement* statements /* [B] or NULL */);
+/* exactly the text after "proof rejected: " of the single verifiers; "" for GLP_VR_NONE or an unknown value */
+const char* glp_verify_reason_text(uint32_t reason);
+/* what the LAST glp_*_verify_batch on this ctx issued, and how many of its proofs ran their queries as items / in place (any pointer may be NULL) */
+int glp_verify_last_batch_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs, uint32_t* n_on_device, uint32_t* n_fallback);
+/* The same two calls for a host WITHOUT a GPU: the same host phase, then the same item bodies one after the other on the host (the constants
+ * arguments of the host verifiers below).  n_on_device / n_fallback (may be NULL): the counts glp_verify_last_batch_counts would give. */
+int glp_plonk_verify_batch_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* const* h_proofs,
+                                const size_t* lens, uint32_t B, const uint64_t* h_circuit_cap, size_t cap_words, const uint64_t* h_public,
+                                size_t n_public, uint32_t min_queries, uint32_t min_pow_bits, glp_verify_verdict* h_verdicts,
+                                uint64_t* h_digests, uint32_t* n_on_device, uint32_t* n_fallback);
+int glp_fri_verify_batch_host(const uint64_t* h_rc, const uint64_t* h_mds_circ, const uint64_t* h_mds_diag, const uint8_t* const* h_proofs,
+                              const size_t* lens, uint32_t B, uint32_t min_queries, uint32_t min_pow_bits, uint32_t min_rate_bits,
+                              glp_verify_verdict* h_verdicts, glp_fri_statement* statements, uint32_t* n_on_device, uint32_t* n_fallback);
+
 /* the public inputs a proof carries: copies min(*n_words, n_public) words to h_out (may be NULL with *n_words = 0) and stores
  * n_public in *n_words.  No verification: GLP_E_INVALID when the bytes are not a circuit proof of this format. */
 int glp_plonk_proof_public_inputs(const uint8_t* h_proof, size_t proof_len, uint64_t* h_out, size_t* n_words);
