@@ -90,6 +90,45 @@ class Ed25519InputLayout(ctypes.Structure):
 ED25519_FORM_PLAIN, ED25519_FORM_FLAGGED, ED25519_FORM_VOTE = 0, 1, 2
 ED25519_IN_OK, ED25519_IN_REJECT, ED25519_IN_NO_PAIR, ED25519_IN_INVALID = 0, 1, 2, 3
 
+
+class HeaderChainLayout(ctypes.Structure):
+    """glp_header_chain_layout: what a header-chain leaf recording fixes — the byte lengths of the 14 field encodings, the headers per leaf and
+    the varint bytes of a height"""
+    _fields_ = [("field_len", ctypes.c_uint32 * 14), ("leaf_headers", ctypes.c_uint32), ("n_groups", ctypes.c_uint32)]
+
+    @classmethod
+    def of(cls, field_lengths, leaf_headers, n_groups):
+        if len(field_lengths) != 14:
+            raise GlpError("a header has 14 field encodings")
+        return cls((ctypes.c_uint32 * 14)(*[int(x) for x in field_lengths]), int(leaf_headers), int(n_groups))
+
+    def header_bytes(self):
+        return sum(self.field_len)
+
+    def n_words(self):
+        n = ctypes.c_uint64()
+        if load_library().glp_header_chain_leaf_input_words(ctypes.byref(self), ctypes.byref(n)) != 0:
+            raise GlpError("no leaf statement has this header layout")
+        return int(n.value)
+
+
+HEADER_CHAIN_OK, HEADER_CHAIN_BAD_LINK, HEADER_CHAIN_BAD_HEIGHT, HEADER_CHAIN_BAD_DATA_FIELD = 0, 1, 2, 3
+TM_BATCH_MAX_LEAVES = 512
+
+
+class DeviceRows:
+    """rows [lo, hi) of a resident [n][stride] u64 buffer, for WitnessProgram.evaluate_device(d_inputs=): a view — free() releases nothing"""
+
+    def __init__(self, buf, stride_words, lo, hi):
+        self.buf, self.ptr, self.nbytes = buf, buf.ptr + lo * stride_words * 8, (hi - lo) * stride_words * 8
+
+    def __int__(self):
+        return self.ptr
+
+    def free(self):
+        self.ptr = None
+
+
 CHECK_GATE, CHECK_COPY = 0, 1
 CHECK_KIND_NAMES = {CHECK_GATE: "gate", CHECK_COPY: "copy"}
 
@@ -351,6 +390,15 @@ def load_library():
         "glp_ed25519_last_input_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "glp_ed25519_half_scalars": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp]),
         "glp_tm_merkle_root": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp]),
+        "glp_tm_merkle_root_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
+        "glp_tm_merkle_root_batch_last_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
+        "glp_tm_merkle_root_batch_host": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+        "glp_header_chain_leaf_input_words": (ctypes.c_int, [ctypes.POINTER(HeaderChainLayout), ctypes.POINTER(ctypes.c_uint64)]),
+        "glp_header_chain_leaf_inputs": (ctypes.c_int, [_vp, ctypes.POINTER(HeaderChainLayout), _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp,
+                                                        ctypes.c_size_t, _vp, _vp]),
+        "glp_header_chain_last_input_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
+        "glp_header_chain_leaf_inputs_host": (ctypes.c_int, [ctypes.POINTER(HeaderChainLayout), _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp,
+                                                             ctypes.c_size_t, _vp, _vp]),
         "glp_challenger_new": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
         "glp_challenger_free": (None, [_vp]),
         "glp_challenger_observe": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
@@ -1325,6 +1373,75 @@ class Prover:
         d.free()
         do.free()
         return out.raw
+
+    def tm_merkle_root_batch(self, trees, download=True):
+        """the Tendermint simple Merkle roots of SEVERAL trees in one call (glp_tm_merkle_root_batch: two launches, one synchronise): trees =
+        a list of lists of leaves (bytes), of any leaf counts (<= TM_BATCH_MAX_LEAVES each) and lengths.  Returns the list of 32-byte roots;
+        download=False: the DeviceBuffer [B][32] in place of the host copy.  The C call then does not synchronise (its counter reads 0), but
+        this wrapper does, once, before it frees the leaf bytes it uploaded: a caller that needs no synchronise at all keeps its bytes resident
+        and calls glp_tm_merkle_root_batch itself."""
+        B = len(trees)
+        leaves = [bytes(x) for t in trees for x in t]
+        first = np.zeros(B + 1, dtype=np.uint64)
+        first[1:] = np.cumsum([len(t) for t in trees])
+        offs = np.zeros(len(leaves) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(x) for x in leaves])
+        blob = b"".join(leaves) or b"\0"
+        d = self.to_device(np.frombuffer(blob, dtype=np.uint8))
+        d_roots = self.alloc(max(8, 32 * B))
+        out = np.zeros((B, 32), dtype=np.uint8)
+        try:
+            self._chk(self.lib.glp_tm_merkle_root_batch(self.ctx, d.ptr, len(blob), offs.ctypes.data, first.ctypes.data, len(leaves), B,
+                                                        d_roots.ptr, out.ctypes.data if download else None), "glp_tm_merkle_root_batch")
+        finally:
+            if not download:
+                self.sync()                     # the blob is freed below: the kernels that read it must be done
+            d.free()
+        if not download:
+            return d_roots
+        d_roots.free()
+        return [out[i].tobytes() for i in range(B)]
+
+    def tm_merkle_root_batch_last_counts(self):
+        """(launches, stream synchronises) of the last glp_tm_merkle_root_batch on this prover"""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        self._chk(self.lib.glp_tm_merkle_root_batch_last_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_tm_merkle_root_batch_last_counts")
+        return tuple(x.value for x in v)
+
+    def header_chain_leaf_inputs(self, layout, d_headers, start_hash, first_height, n, out=None, hashes=None):
+        """the input vectors of the header-chain leaves of n headers that lie on the device (glp_header_chain_leaf_inputs: at most 4 launches,
+        one synchronise): (DeviceBuffer [n / leaf_headers][layout.n_words()] u64, status int32[n] of HEADER_CHAIN_*, DeviceBuffer [n + 1][32] of
+        the start hash and every header's hash).  Row l equals data_commitment_mr._chain_leaf_inputs of leaf l; the row of a leaf with a refused
+        header is zero.  d_headers: n * layout.header_bytes() bytes (DeviceBuffer / pointer).  out / hashes: DeviceBuffers to reuse."""
+        width, n = layout.n_words(), int(n)
+        if n % layout.leaf_headers:
+            raise GlpError("the chain is not a whole number of leaves")
+        start = np.frombuffer(bytes(start_hash), dtype=np.uint8).copy()
+        if start.size != 32:
+            raise GlpError("the start hash has 32 bytes")
+        need = max(8, (n // layout.leaf_headers) * width * 8)
+        own = []                                                    # what this call allocates: freed again when the C call refuses
+        if out is None or out.ptr is None or out.nbytes < need:
+            out = self.alloc(need)
+            own.append(out)
+        if hashes is None or hashes.ptr is None or hashes.nbytes < 32 * (n + 1):
+            hashes = self.alloc(32 * (n + 1))
+            own.append(hashes)
+        status = np.zeros(max(1, n), dtype=np.int32)
+        try:
+            self._chk(self.lib.glp_header_chain_leaf_inputs(self.ctx, ctypes.byref(layout), _ptr(d_headers), start.ctypes.data, int(first_height), n,
+                                                            out.ptr, width, hashes.ptr, status.ctypes.data), "glp_header_chain_leaf_inputs")
+        except Exception:
+            for b in own:
+                b.free()
+            raise
+        return out, status[:n], hashes
+
+    def header_chain_last_input_counts(self):
+        """(launches, stream synchronises) of the last header_chain_leaf_inputs on this prover"""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        self._chk(self.lib.glp_header_chain_last_input_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_header_chain_last_input_counts")
+        return tuple(x.value for x in v)
 
     def transpose(self, mat):
         m = np.ascontiguousarray(mat, dtype=np.uint64)

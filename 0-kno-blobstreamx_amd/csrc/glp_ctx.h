@@ -71,6 +71,9 @@ struct glp_ctx {
     hipEvent_t place_ev = nullptr;
     // what the last glp_ed25519_leaf_inputs issued: kernel launches, stream synchronises (glp_ed25519_last_input_counts)
     uint32_t ed_input_counts[2] = {0, 0};
+    // the same of the last glp_tm_merkle_root_batch and of the last glp_header_chain_leaf_inputs
+    uint32_t tm_batch_counts[2] = {0, 0};
+    uint32_t chain_input_counts[2] = {0, 0};
 };
 
 // stage timing tree of the prover drivers (the TimingTree of the upstream prover, recalled): a

@@ -478,3 +478,149 @@ extern "C" int glp_ed25519_half_scalars(glp_ctx* c, const uint64_t* d_k, uint64_
     GLP_HIPCHK(c, hipGetLastError());
     return GLP_OK;
 }
+
+// ---- B Tendermint trees per call (tm_batch_kernels.cuh) and the header-chain leaf's input vectors (chain_inputs.cuh) -------------------------
+#include "chain_inputs.cuh"
+static_assert(GLP_CHAIN_OK == GLP_HEADER_CHAIN_OK && GLP_CHAIN_BAD_LINK == GLP_HEADER_CHAIN_BAD_LINK &&
+              GLP_CHAIN_BAD_HEIGHT == GLP_HEADER_CHAIN_BAD_HEIGHT && GLP_CHAIN_BAD_DATA_FIELD == GLP_HEADER_CHAIN_BAD_DATA_FIELD &&
+              GLP_CHAIN_FIELDS == sizeof(((glp_header_chain_layout*)0)->field_len) / sizeof(uint32_t),
+              "glprover.h and chain_inputs.cuh name the same codes");
+
+// the two launches over a.total_leaves leaves and a.n_trees (> 0) trees none of which has more than max_tree leaves; a.nodes is set here
+static int tm_batch_launch(glp_ctx* c, GlpTmBatchArgs& a, u64 max_tree, GlpPoolBuf& nodes, uint32_t* launches) {
+    if (a.n_trees > 0x7fffffffull || a.total_leaves > (1ull << 36)) { glp_set_err(c, "glp_tm_merkle_root_batch: too many trees or leaves"); return GLP_E_UNSUPPORTED; }
+    int rc = ensure_sha_tables(c);
+    if (rc) return rc;
+    if (nodes.alloc((size_t)(a.total_leaves ? a.total_leaves : 1) * 32) != hipSuccess) return GLP_E_NOMEM;
+    a.nodes = (u32*)nodes.p;
+    a.k256 = c->hash->d_k256;
+    if (a.total_leaves) {
+        hipLaunchKernelGGL(glp_tm_batch_leaf_kernel<0>, dim3((unsigned)((a.total_leaves + 255) / 256)), dim3(256), 0, c->stream, a);
+        (*launches)++;
+    }
+    if (max_tree <= 2 * GLP_TM_BATCH_LANES_SMALL)
+        hipLaunchKernelGGL(glp_tm_batch_fold_kernel<GLP_TM_BATCH_LANES_SMALL>, dim3((unsigned)a.n_trees), dim3(GLP_TM_BATCH_LANES_SMALL), 0, c->stream, a);
+    else
+        hipLaunchKernelGGL(glp_tm_batch_fold_kernel<GLP_TM_BATCH_LANES>, dim3((unsigned)a.n_trees), dim3(GLP_TM_BATCH_LANES), 0, c->stream, a);
+    (*launches)++;
+    GLP_HIPCHK(c, hipGetLastError());
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_merkle_root_batch(glp_ctx* c, const uint8_t* d_data, uint64_t data_len, const uint64_t* h_leaf_offsets,
+                                        const uint64_t* h_tree_first, uint64_t total_leaves, uint64_t n_trees, uint8_t* d_roots,
+                                        uint8_t* h_roots) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->tm_batch_counts[0] = c->tm_batch_counts[1] = 0;
+    if (n_trees == 0) return GLP_OK;
+    if (!h_leaf_offsets || !h_tree_first || !d_roots || (!d_data && data_len)) { glp_set_err(c, "glp_tm_merkle_root_batch: null argument"); return GLP_E_INVALID; }
+    const int bad = glp_tm_batch_check(h_leaf_offsets, h_tree_first, total_leaves, n_trees, data_len);
+    if (bad == 1) { glp_set_err(c, "glp_tm_merkle_root_batch: offsets decrease, pass data_len, or the trees do not cover the leaves"); return GLP_E_INVALID; }
+    if (bad == 2) { glp_set_err(c, "glp_tm_merkle_root_batch: a tree has more than %d leaves", GLP_TM_BATCH_MAX_LEAVES); return GLP_E_UNSUPPORTED; }
+    u64 max_tree = 0;
+    for (u64 t = 0; t < n_trees; t++) max_tree = h_tree_first[t + 1] - h_tree_first[t] > max_tree ? h_tree_first[t + 1] - h_tree_first[t] : max_tree;
+    // the kernels read the checked words themselves: uploaded here, stream-ordered, into scratch of the ctx
+    GlpPoolBuf nodes(c), arrays(c);
+    const size_t n_off = (size_t)total_leaves + 1, n_first = (size_t)n_trees + 1;
+    if (arrays.alloc((n_off + n_first) * 8) != hipSuccess) return GLP_E_NOMEM;
+    GLP_HIPCHK(c, hipMemcpyAsync(arrays.u(), h_leaf_offsets, n_off * 8, hipMemcpyHostToDevice, c->stream));
+    GLP_HIPCHK(c, hipMemcpyAsync(arrays.u() + n_off, h_tree_first, n_first * 8, hipMemcpyHostToDevice, c->stream));
+    GlpTmBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.data = d_data; a.leaf_off = arrays.u(); a.tree_first = arrays.u() + n_off; a.n_trees = n_trees; a.total_leaves = total_leaves; a.roots = d_roots;
+    int rc = tm_batch_launch(c, a, max_tree, nodes, &c->tm_batch_counts[0]);
+    if (rc) return rc;
+    if (h_roots) {
+        GLP_HIPCHK(c, hipMemcpyAsync(h_roots, d_roots, (size_t)n_trees * 32, hipMemcpyDeviceToHost, c->stream));
+        c->tm_batch_counts[1] = 1;
+        GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_merkle_root_batch_last_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs) {
+    if (!c || !n_launches || !n_host_syncs) return GLP_E_INVALID;
+    *n_launches = c->tm_batch_counts[0];
+    *n_host_syncs = c->tm_batch_counts[1];
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_merkle_root_batch_host(const uint8_t* data, uint64_t data_len, const uint64_t* leaf_offsets, const uint64_t* tree_first,
+                                             uint64_t total_leaves, uint64_t n_trees, uint8_t* roots) {
+    if (n_trees == 0) return GLP_OK;
+    if (!leaf_offsets || !tree_first || !roots || (!data && data_len)) return GLP_E_INVALID;
+    const int bad = glp_tm_batch_check(leaf_offsets, tree_first, total_leaves, n_trees, data_len);
+    if (bad) return bad == 1 ? GLP_E_INVALID : GLP_E_UNSUPPORTED;
+    GlpTmBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.data = data; a.leaf_off = leaf_offsets; a.tree_first = tree_first; a.n_trees = n_trees; a.total_leaves = total_leaves; a.roots = roots; a.k256 = K256;
+    std::vector<u32> scratch(8 * GLP_TM_BATCH_MAX_LEAVES);
+    for (u64 t = 0; t < n_trees; t++) glp_tm_batch_tree_host(a, t, scratch.data());
+    return GLP_OK;
+}
+
+extern "C" int glp_header_chain_leaf_input_words(const glp_header_chain_layout* layout, uint64_t* n_words) {
+    if (!layout || !n_words) return GLP_E_INVALID;
+    const u64 per = glp_chain_words_per_header(layout->field_len, layout->leaf_headers, layout->n_groups);
+    if (!per) return GLP_E_INVALID;
+    *n_words = GLP_CHAIN_ROW_HEAD + per * layout->leaf_headers;
+    return GLP_OK;
+}
+
+extern "C" int glp_header_chain_leaf_inputs(glp_ctx* c, const glp_header_chain_layout* layout, const uint8_t* d_headers, const uint8_t* start_hash32,
+                                            uint64_t first_height, uint64_t n, uint64_t* d_inputs, size_t input_stride, uint8_t* d_hashes,
+                                            int32_t* h_status) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->chain_input_counts[0] = c->chain_input_counts[1] = 0;
+    uint64_t width = 0;
+    if (glp_header_chain_leaf_input_words(layout, &width) != GLP_OK) { glp_set_err(c, "glp_header_chain_leaf_inputs: no leaf statement has this layout"); return GLP_E_INVALID; }
+    if (n == 0) return GLP_OK;
+    if (!d_headers || !start_hash32 || !d_inputs || !h_status) { glp_set_err(c, "glp_header_chain_leaf_inputs: null argument"); return GLP_E_INVALID; }
+    if (n % layout->leaf_headers || input_stride < width || n > (1ull << 30) || first_height >= (1ull << 49)) {
+        glp_set_err(c, "glp_header_chain_leaf_inputs: n is not a whole number of leaves or above 2^30, the stride is below the row, or first_height is 2^49 or more");
+        return GLP_E_INVALID;
+    }
+    GlpPoolBuf nodes(c), stat(c), hashes(c);
+    if (stat.alloc((size_t)n * sizeof(int32_t)) != hipSuccess) return GLP_E_NOMEM;
+    if (!d_hashes) {
+        if (hashes.alloc((size_t)(n + 1) * 32) != hipSuccess) return GLP_E_NOMEM;
+        d_hashes = (uint8_t*)hashes.p;
+    }
+    GlpChainArgs a;
+    GlpTmBatchArgs t;
+    memset(&t, 0, sizeof(t));
+    if (glp_header_chain_fill_args(a, t, layout->field_len, layout->leaf_headers, layout->n_groups, d_headers, start_hash32, first_height, n, d_inputs,
+                                   input_stride, d_hashes, (int32_t*)stat.p, nullptr, nullptr)) return GLP_E_INVALID;
+    int rc = tm_batch_launch(c, t, GLP_CHAIN_FIELDS, nodes, &c->chain_input_counts[0]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(glp_header_chain_check_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(glp_header_chain_rows_kernel<0>, dim3((unsigned)n), dim3(64), 0, c->stream, a);
+    c->chain_input_counts[0] += 2;
+    GLP_HIPCHK(c, hipGetLastError());
+    GLP_HIPCHK(c, hipMemcpyAsync(h_status, stat.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    c->chain_input_counts[1] = 1;
+    GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+
+extern "C" int glp_header_chain_last_input_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs) {
+    if (!c || !n_launches || !n_host_syncs) return GLP_E_INVALID;
+    *n_launches = c->chain_input_counts[0];
+    *n_host_syncs = c->chain_input_counts[1];
+    return GLP_OK;
+}
+
+extern "C" int glp_header_chain_leaf_inputs_host(const glp_header_chain_layout* layout, const uint8_t* headers, const uint8_t* start_hash32,
+                                                 uint64_t first_height, uint64_t n, uint64_t* inputs, size_t input_stride, uint8_t* hashes,
+                                                 int32_t* status) {
+    uint64_t width = 0;
+    if (glp_header_chain_leaf_input_words(layout, &width) != GLP_OK) return GLP_E_INVALID;
+    if (n == 0) return GLP_OK;
+    if (!headers || !start_hash32 || !inputs || !status || n % layout->leaf_headers || input_stride < width || first_height >= (1ull << 49)) return GLP_E_INVALID;
+    std::vector<uint8_t> own;
+    if (!hashes) { own.resize((size_t)(n + 1) * 32); hashes = own.data(); }
+    return glp_header_chain_leaf_inputs_host_impl(layout->field_len, layout->leaf_headers, layout->n_groups, headers, start_hash32, first_height, n,
+                                                  inputs, input_stride, hashes, status, K256) ? GLP_E_INVALID : GLP_OK;
+}

@@ -654,11 +654,19 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
 
     def __init__(self, prover, poseidon_consts, leaf_headers=8, fan_in=8, num_queries=28, pow_bits=16, map_provers=(), height_varint_bytes=4,
                  field_lengths=(4, 12, 5, 13, 72, 34, 34, 34, 34, 34, 34, 34, 34, 22), defer_commitment=None, device_witness=False,
-                 device_witness_chunk=32, prove_batch=0, check_witness=False):
-        """defer_commitment (default: leaves of 8 or more headers): the leaves expose their headers' data hashes and the LEVEL-1 NODES hash the
+                 device_witness_chunk=32, prove_batch=0, check_witness=False, device_inputs=False):
+        """device_inputs (default off; needs device_witness): the leaves' INPUT VECTORS are built on the device too.  prove_chain,
+        prove_chain_distributed and _map_chain upload the headers of this rank's share once and make ONE Prover.header_chain_leaf_inputs call
+        over the whole share (the header hashes by the batched tree kernels, the link / height / data-field tests, the rows); the device
+        evaluator reads device_witness_chunk rows at a time from that resident buffer where they lie.  header_hash, the validation loop and
+        _chain_leaf_inputs are not run; the same refusals, the same proofs, byte for byte.
+        defer_commitment (default: leaves of 8 or more headers): the leaves expose their headers' data hashes and the LEVEL-1 NODES hash the
         (height, data_hash) tuples and the leaf subtrees — round 3: an 8-header leaf is 368 compressions x 178 rows = 2.7k rows past 2^16; without
         its 30 tuple / subtree compressions it fits 2^16 rows (half the leaf proof), and the node circuit (75k of 131k rows used) has the room.
         The statement of every node — hence of the root — is unchanged; a chain of ONE leaf has no node and is refused in this mode."""
+        if device_inputs and not device_witness:
+            raise ValueError("device_inputs needs device_witness=True: the rows it builds are read by the device evaluator")
+        self.device_inputs = bool(device_inputs)
         super().__init__(prover, poseidon_consts, leaf_blocks=leaf_headers, fan_in=fan_in, num_queries=num_queries, pow_bits=pow_bits,
                          map_provers=map_provers, device_witness=device_witness, device_witness_chunk=device_witness_chunk, prove_batch=prove_batch,
                          check_witness=check_witness)
@@ -755,9 +763,14 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
             raise ValueError("the chain is not a whole number of leaves")
         if self.leaf_program is None:
             self._record_leaf()
-        hashes = [bytes(start_hash)] + [self.header_hash(h) for h in headers]           # host side: the start hash of every leaf
-        t0 = time.perf_counter()
-        leaves = self._map_chain(hashes, first_height, headers, 0, n)
+        end_hash = None
+        if self.device_inputs:
+            t0 = time.perf_counter()
+            leaves, end_hash = self._map_chain_device(start_hash, first_height, headers, 0, n)
+        else:
+            hashes = [bytes(start_hash)] + [self.header_hash(h) for h in headers]       # host side: the start hash of every leaf
+            t0 = time.perf_counter()
+            leaves = self._map_chain(hashes, first_height, headers, 0, n)
         t1 = time.perf_counter()
         levels = []
         if len(leaves) == 1:
@@ -770,11 +783,13 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
         t2 = time.perf_counter()
         return {"root_proof": root_proof, "public": public, "key": key, "leaves": len(leaves), "map_seconds": round(t1 - t0, 4),
                 "reduce_seconds": round(t2 - t1, 4), "levels": levels, "record_seconds": dict(self.record_seconds),
-                "end_hash": b"".join(struct.pack(">I", v) for v in public[8:16]), "commitment": b"".join(struct.pack(">I", v) for v in public[16:24])}
+                "end_hash": end_hash if end_hash is not None else b"".join(struct.pack(">I", v) for v in public[8:16]), "commitment": b"".join(struct.pack(">I", v) for v in public[16:24])}
 
     def _map_chain(self, hashes, first_height, headers, lo, hi):
         """leaf proofs of headers[lo:hi] (a whole number of leaves), on every prover this object has; hashes[k] = hash of the header BEFORE header k"""
         B = self.leaf_blocks
+        if self.device_inputs:                                       # hashes: only the one before header lo is read
+            return self._map_chain_device(hashes[lo], first_height, headers, lo, hi)[0]
         for k in range(lo, hi, B):
             if any(tuple(len(bytes(f)) for f in h) != self.field_lengths for h in headers[k:k + B]):
                 raise ValueError("a leaf takes leaf_headers headers whose field encodings have the recorded lengths")
@@ -791,6 +806,39 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
                 raise ValueError(f"header {k}: the height field is not the encoding of {first_height + k}, or the data-hash field is malformed")
         return self._map_inputs([_chain_leaf_inputs(hashes[k], first_height + k, headers[k:k + B], self.n_groups) for k in range(lo, hi, B)])
 
+    def _map_chain_device(self, prev_hash, first_height, headers, lo, hi):
+        """_map_chain with the input vectors built on the device (device_inputs): (leaf proofs of headers[lo:hi], the hash of header hi - 1 as the
+        device computed it).  prev_hash: the hash of the header before header lo; first_height: the height of header 0.  ONE upload of the
+        share's bytes, ONE glp_header_chain_leaf_inputs call, then the Map loop of _map_inputs_device on row ranges of the resident buffer.
+        The refusals are _map_chain's, with the same header index."""
+        pkg = importlib.import_module(__package__)
+        if self.leaf_program is None:
+            self._record_leaf()
+        layout = pkg.HeaderChainLayout.of(self.field_lengths, self.leaf_blocks, self.n_groups)
+        width, n = layout.n_words(), hi - lo
+        if width != self.leaf_program.n_inputs:
+            raise ValueError("the recorded leaf takes other inputs than the device builds")
+        blob = b"".join(bytes(f) for h in headers[lo:hi] for f in h)
+        if len(blob) != n * layout.header_bytes() or any(tuple(map(len, h)) != self.field_lengths for h in headers[lo:hi]):
+            raise ValueError("a leaf takes leaf_headers headers whose field encodings have the recorded lengths")
+        d_hdr = self.prover.to_device(np.frombuffer(blob or b"\0", dtype=np.uint8))
+        d_in = d_hashes = None
+        try:
+            d_in, status, d_hashes = self.prover.header_chain_leaf_inputs(layout, d_hdr, prev_hash, first_height + lo, n)
+            bad = np.flatnonzero(status)
+            if bad.size:
+                k = lo + int(bad[0])
+                if status[bad[0]] == pkg.HEADER_CHAIN_BAD_LINK:
+                    raise ValueError(f"header {k} does not name its predecessor's hash in its last_block_id")
+                raise ValueError(f"header {k}: the height field is not the encoding of {first_height + k}, or the data-hash field is malformed")
+            leaves = self._map_inputs_device(n // self.leaf_blocks, resident=lambda a, b, buf: pkg.DeviceRows(d_in, width, a, b))
+            end_hash = d_hashes.download((32,), dtype=np.uint8, offset_bytes=32 * n).tobytes()
+        finally:
+            for b in (d_hdr, d_in, d_hashes):
+                if b is not None:
+                    b.free()
+        return leaves, end_hash
+
     def prove_chain_distributed(self, start_hash, first_height, headers, device=None, comm=None):
         """prove_chain with the work spread over the ranks (mapreduce.reduce_tree_distributed): rank r proves and folds the r-th contiguous part of
         the chain on its own GPU, ONE all-gather of the node proofs, rank 0 folds the root (its nodes check that the parts are adjacent).  Every rank
@@ -802,8 +850,11 @@ class HeaderChainMapReduce(DataCommitmentMapReduce):
             raise ValueError("the chain is not a whole number of leaves per rank")
         if self.leaf_program is None:
             self._record_leaf()
-        hashes = [bytes(start_hash)] + [self.header_hash(h) for h in headers]
         per = n // world
+        if self.device_inputs:                                       # only the hash before this rank's share is needed on the host: one tree
+            hashes = {rank * per: bytes(start_hash) if rank == 0 else self.header_hash(headers[rank * per - 1])}
+        else:
+            hashes = [bytes(start_hash)] + [self.header_hash(h) for h in headers]
         state, levels = {}, []
 
         def fold_local(_):

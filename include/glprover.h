@@ -714,6 +714,64 @@ int glp_tm_merkle_root(glp_ctx* ctx, const uint8_t* d_leaves, uint32_t leaf_len,
 int glp_tm_merkle_root_var(glp_ctx* ctx, const uint8_t* d_data, uint64_t data_len, const uint64_t* d_offsets, uint64_t n,
                            uint8_t* h_root32);
 
+/* n_trees such trees in ONE stream-ordered call: tree t has the leaves [tree_first[t], tree_first[t + 1]) of one numbering over all trees,
+ * leaf i = d_data[leaf_offsets[i] .. leaf_offsets[i + 1]) — the _var form's offsets across all trees.  The trees of a call may differ in leaf
+ * count and leaf lengths; a tree without leaves gives what glp_tm_merkle_root_var gives for n = 0 (SHA-256 of nothing).  d_roots [n_trees][32]
+ * stays on the device.  Two launches whatever n_trees is (a work-item per leaf for the leaf hashes; a workgroup per tree folding the levels
+ * through LDS) and NO synchronise and no copy to the host, unless h_roots is not NULL: then one copy of all n_trees roots and one synchronise.
+ * The two arrays are validated ON THE HOST, from the host's copy of them, before anything is launched — h_leaf_offsets [total_leaves + 1]
+ * non-decreasing with the last <= data_len, h_tree_first [n_trees + 1] ascending from 0 to total_leaves: GLP_E_INVALID otherwise, and nothing is
+ * written.  The call uploads the checked words itself, stream-ordered, into scratch of the ctx, and the kernels read no other offset: there is
+ * no device copy for the caller to keep in step.  The two host arrays must stay as they are until the stream has passed the call (h_roots,
+ * glp_sync or any later synchronising call).
+ * A tree of more than GLP_TM_BATCH_MAX_LEAVES leaves (one workgroup's LDS level: 256 nodes after the first pairing) gives GLP_E_UNSUPPORTED
+ * and writes nothing; use glp_tm_merkle_root_var for such a tree.  Validator sets of 100 - 150 and the 14 fields of a header are far below it.
+ * n_trees == 0 is GLP_OK.  glp_tm_merkle_root_batch_last_counts: launches and synchronises of the LAST call on the ctx.
+ * glp_tm_merkle_root_batch_host: the same trees serially on the host with the kernels' per-item functions; no ctx, no GPU. */
+#define GLP_TM_BATCH_MAX_LEAVES 512
+int glp_tm_merkle_root_batch(glp_ctx* ctx, const uint8_t* d_data, uint64_t data_len, const uint64_t* h_leaf_offsets, const uint64_t* h_tree_first,
+                             uint64_t total_leaves, uint64_t n_trees, uint8_t* d_roots, uint8_t* h_roots);
+int glp_tm_merkle_root_batch_last_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
+int glp_tm_merkle_root_batch_host(const uint8_t* data, uint64_t data_len, const uint64_t* leaf_offsets, const uint64_t* tree_first,
+                                  uint64_t total_leaves, uint64_t n_trees, uint8_t* roots);
+
+/* The INPUT VECTORS of the header-chain leaf on the device: from the raw headers of a chain to the rows glp_witness_eval_device reads.
+ * d_headers: n headers, each the concatenation of its 14 field encodings at the layout's lengths (field_len: what the leaf recording fixes;
+ * leaf_headers: headers per leaf; n_groups: the varint bytes of a height).  Three steps, at most 4 launches and ONE synchronise (after the
+ * copy of the statuses to h_status[n]) whatever n is:
+ *   1. the n header hashes: the batched tree kernels over n trees of 14 leaves, read at the layout's offsets (no offset array exists);
+ *   2. one work-item per header k tests what the leaf circuit will build instead of reading: field 4 begins 0a 20 || hash of header k - 1
+ *      (start_hash32 for k = 0), field 2 is 08 || varint(first_height + k) in exactly n_groups bytes (a non-minimal or over-long varint is not),
+ *      field 6 begins 0a 20 -> GLP_HEADER_CHAIN_OK / _BAD_LINK / _BAD_HEIGHT / _BAD_DATA_FIELD, the first that applies in this order;
+ *   3. row l of d_inputs ([n / leaf_headers][input_stride] words, input_stride >= glp_header_chain_leaf_input_words) = the 8 big-endian words
+ *      of the hash before header l * leaf_headers, the height first_height + l * leaf_headers, then per header: the varint groups (low first),
+ *      the 32 data-hash bytes, the bytes of last_block_id behind its hash, the bytes of the eleven other fields — one byte per word.  A leaf
+ *      with a header whose status is not OK gets an all-zero row: none is written partially.  Words past the row's width are left alone.
+ * d_hashes ([n + 1][32]: start hash, then the hash of every header) may be NULL.  n == 0 is GLP_OK; GLP_E_INVALID for n that is not a multiple
+ * of leaf_headers or above 2^30, first_height >= 2^49 (heights are below 2^49: 7 varint bytes), a null argument, a stride below the row, or a
+ * layout no leaf statement has (field 4 below 34 bytes, field 6 not 34 bytes, a field above 65536 bytes, n_groups outside 1 .. 7, leaf_headers
+ * outside 1 .. 1024: every wave of the row kernel reads its leaf's leaf_headers statuses, which is meant for leaves of a few headers — the
+ * statements use 1 to 8).  glp_header_chain_leaf_input_words needs no GPU and no ctx.  glp_header_chain_last_input_counts: launches and
+ * synchronises of the LAST call on the ctx.  glp_header_chain_leaf_inputs_host: the same three steps serially on the host with the kernels'
+ * per-item functions (hashes [n + 1][32] may be NULL); no ctx, no GPU. */
+#define GLP_HEADER_CHAIN_OK 0
+#define GLP_HEADER_CHAIN_BAD_LINK 1
+#define GLP_HEADER_CHAIN_BAD_HEIGHT 2
+#define GLP_HEADER_CHAIN_BAD_DATA_FIELD 3
+typedef struct {
+    uint32_t field_len[14];
+    uint32_t leaf_headers;
+    uint32_t n_groups;
+} glp_header_chain_layout;
+int glp_header_chain_leaf_input_words(const glp_header_chain_layout* layout, uint64_t* n_words);
+int glp_header_chain_leaf_inputs(glp_ctx* ctx, const glp_header_chain_layout* layout, const uint8_t* d_headers, const uint8_t* start_hash32,
+                                 uint64_t first_height, uint64_t n, uint64_t* d_inputs, size_t input_stride, uint8_t* d_hashes,
+                                 int32_t* h_status);
+int glp_header_chain_last_input_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
+int glp_header_chain_leaf_inputs_host(const glp_header_chain_layout* layout, const uint8_t* headers, const uint8_t* start_hash32,
+                                      uint64_t first_height, uint64_t n, uint64_t* inputs, size_t input_stride, uint8_t* hashes,
+                                      int32_t* status);
+
 /* ---- Multi-GPU exchange (row a11 / SURVEY §8e, §8(b) glp_allgather_proofs; upstream name recalled: plonky2x mapreduce) ----
  * Leaf subproofs shard one per GPU, one process (and one ctx) per GPU.  The exchange is ONE RCCL all-gather of fixed-size
  * blocks over xGMI, on the ctx's stream.  Bootstrap as NCCL does: rank 0 makes the id and hands its GLP_COMM_ID_BYTES bytes
