@@ -114,6 +114,8 @@ class HeaderChainLayout(ctypes.Structure):
 
 HEADER_CHAIN_OK, HEADER_CHAIN_BAD_LINK, HEADER_CHAIN_BAD_HEIGHT, HEADER_CHAIN_BAD_DATA_FIELD = 0, 1, 2, 3
 TM_BATCH_MAX_LEAVES = 512
+TM_FOREST_MAX_LEAVES = 1 << 24
+TM_INCLUSION_OK, TM_INCLUSION_BAD_SHAPE, TM_INCLUSION_BAD_ROOT = 0, 1, 2
 
 
 class DeviceRows:
@@ -393,6 +395,19 @@ def load_library():
         "glp_tm_merkle_root_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
         "glp_tm_merkle_root_batch_last_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "glp_tm_merkle_root_batch_host": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+        "glp_tm_forest_create": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.POINTER(_vp)]),
+        "glp_tm_forest_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(ctypes.c_uint64)]),
+        "glp_tm_forest_roots": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+        "glp_tm_forest_destroy": (ctypes.c_int, [_vp]),
+        "glp_tm_forest_proofs": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint32, _vp, _vp]),
+        "glp_tm_verify_inclusion_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                                         ctypes.c_uint64, _vp]),
+        "glp_tm_forest_last_counts": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint32)] * 2),
+        "glp_tm_forest_proofs_host": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, _vp,
+                                                     ctypes.c_uint32, _vp, _vp]),
+        "glp_tm_verify_inclusion_batch_host": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                                              ctypes.c_uint64, _vp]),
         "glp_header_chain_leaf_input_words": (ctypes.c_int, [ctypes.POINTER(HeaderChainLayout), ctypes.POINTER(ctypes.c_uint64)]),
         "glp_header_chain_leaf_inputs": (ctypes.c_int, [_vp, ctypes.POINTER(HeaderChainLayout), _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp,
                                                         ctypes.c_size_t, _vp, _vp]),
@@ -1408,6 +1423,57 @@ class Prover:
         self._chk(self.lib.glp_tm_merkle_root_batch_last_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_tm_merkle_root_batch_last_counts")
         return tuple(x.value for x in v)
 
+    def tm_forest(self, trees, roots=False):
+        """the Tendermint simple Merkle trees of `trees` (a list of lists of leaves, any counts up to TM_FOREST_MAX_LEAVES and any lengths) with
+        EVERY LEVEL KEPT on the device (glp_tm_forest_create): a TmForest that hands out roots and audit paths until .free().  roots=True: the
+        call copies the roots to the host at once (its one synchronise)."""
+        return TmForest(self, trees, roots)
+
+    def tm_verify_inclusion_batch(self, roots, proofs, leaves, root_of=None):
+        """check n inclusion proofs in one launch (glp_tm_verify_inclusion_batch): roots = list of 32-byte roots, proofs[p] = (total, index,
+        leaf_hash, aunts) as TmForest.proofs gives them (the leaf hash is NOT read: leaves[p], the leaf BYTES, are hashed on the device),
+        root_of[p] = the root proof p is checked against (None: root 0).  Returns int32[n] of TM_INCLUSION_OK / _BAD_SHAPE / _BAD_ROOT."""
+        n = len(proofs)
+        if len(leaves) != n or (root_of is not None and len(root_of) != n):
+            raise GlpError("tm_verify_inclusion_batch: proofs, leaves and root_of differ in length")
+        status = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return status
+        stride = max(1, max(len(p[3]) for p in proofs))
+        aunts = np.zeros((n, stride, 32), dtype=np.uint8)
+        for i, p in enumerate(proofs):
+            for k, a in enumerate(p[3]):
+                aunts[i, k] = np.frombuffer(bytes(a), dtype=np.uint8)
+        return self.tm_verify_inclusion_arrays(roots, leaves, [p[1] for p in proofs], [p[0] for p in proofs], aunts, [len(p[3]) for p in proofs], root_of)
+
+    def tm_verify_inclusion_arrays(self, roots, leaves, index, total, aunts, n_aunts, root_of=None):
+        """the array form of tm_verify_inclusion_batch: aunts uint8 [n][aunt_stride][32], index / total / n_aunts the proofs' own (untrusted) words"""
+        n = len(leaves)
+        aunts = np.ascontiguousarray(aunts, dtype=np.uint8)
+        stride = aunts.shape[1] if aunts.ndim == 3 else 0
+        status = np.full(n, -1, dtype=np.int32)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(x) for x in leaves])
+        blob = b"".join(bytes(x) for x in leaves) or b"\0"
+        ro = None if root_of is None else np.ascontiguousarray(root_of, dtype=np.uint32)
+        bufs = [self.to_device(np.frombuffer(b"".join(bytes(r) for r in roots) or b"\0", dtype=np.uint8)), self.to_device(np.frombuffer(blob, dtype=np.uint8)),
+                self.to_device(np.asarray(index, dtype=np.uint64)), self.to_device(np.asarray(total, dtype=np.uint64)), self.to_device(aunts),
+                self.to_device(np.asarray(n_aunts, dtype=np.uint32))]
+        try:
+            self._chk(self.lib.glp_tm_verify_inclusion_batch(self.ctx, bufs[0].ptr, len(roots), None if ro is None else ro.ctypes.data, bufs[1].ptr,
+                                                             int(offs[-1]), offs.ctypes.data, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr, stride, bufs[5].ptr, n,
+                                                             status.ctypes.data), "glp_tm_verify_inclusion_batch")
+        finally:
+            for b in bufs:
+                b.free()
+        return status
+
+    def tm_forest_last_counts(self):
+        """(launches, stream synchronises) of the last glp_tm_forest_create / _proofs / glp_tm_verify_inclusion_batch on this prover"""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        self._chk(self.lib.glp_tm_forest_last_counts(self.ctx, *[ctypes.byref(x) for x in v]), "glp_tm_forest_last_counts")
+        return tuple(x.value for x in v)
+
     def header_chain_leaf_inputs(self, layout, d_headers, start_hash, first_height, n, out=None, hashes=None):
         """the input vectors of the header-chain leaves of n headers that lie on the device (glp_header_chain_leaf_inputs: at most 4 launches,
         one synchronise): (DeviceBuffer [n / leaf_headers][layout.n_words()] u64, status int32[n] of HEADER_CHAIN_*, DeviceBuffer [n + 1][32] of
@@ -1464,6 +1530,95 @@ def sha_pad(msg: bytes, block: int, blocks: int = None) -> bytes:
         assert need == blocks, "message does not pad to the requested number of blocks"
     pad = need * block - len(msg) - 1 - lenbytes
     return msg + b"\x80" + b"\x00" * pad + (8 * len(msg)).to_bytes(lenbytes, "big")
+
+
+class TmForest:
+    """B Tendermint simple Merkle trees with every level kept on the device (glp_tm_forest_*).  The proof format is BUILD-DEFINED (Tendermint's
+    crypto/merkle.Proof restated from memory, unpinned): a proof is the tuple (total, index, leaf_hash, aunts) with the aunts bottom-up."""
+
+    def __init__(self, prover, trees, roots=False):
+        self.prover, self.handle = prover, None
+        self.counts = [len(t) for t in trees]
+        B = len(trees)
+        leaves = [bytes(x) for t in trees for x in t]
+        self.first = np.zeros(B + 1, dtype=np.uint64)
+        self.first[1:] = np.cumsum(self.counts)
+        offs = np.zeros(len(leaves) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(x) for x in leaves])
+        blob = b"".join(leaves) or b"\0"
+        d = prover.to_device(np.frombuffer(blob, dtype=np.uint8))
+        h = _vp()
+        self._roots = np.zeros((B, 32), dtype=np.uint8) if roots else None
+        try:
+            prover._chk(prover.lib.glp_tm_forest_create(prover.ctx, d.ptr, int(offs[-1]), offs.ctypes.data, self.first.ctypes.data, len(leaves), B,
+                                                        self._roots.ctypes.data if roots and B else None, ctypes.byref(h)), "glp_tm_forest_create")
+            self.create_counts = prover.tm_forest_last_counts()
+        finally:
+            if not roots:
+                prover.sync()                   # the blob is freed below: the kernels that read it must be done
+            d.free()
+        self.handle = h
+        prover._circuits.append(self)           # holds a pool block of the ctx: freed before it (Prover.close)
+
+    def info(self):
+        """(trees, leaves, max_aunts, device bytes held)"""
+        v = [ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64()]
+        self.prover._chk(self.prover.lib.glp_tm_forest_info(self.handle, *[ctypes.byref(x) for x in v]), "glp_tm_forest_info")
+        return tuple(x.value for x in v)
+
+    def roots_ptr(self):
+        """the device array [n_trees][32], valid until free()"""
+        p = _vp()
+        self.prover._chk(self.prover.lib.glp_tm_forest_roots(self.handle, ctypes.byref(p)), "glp_tm_forest_roots")
+        return p.value
+
+    def roots(self):
+        """the list of 32-byte roots (copied from the device once, then kept)"""
+        if self._roots is None:
+            B = len(self.counts)
+            self._roots = np.zeros((B, 32), dtype=np.uint8)
+            if B:
+                self.prover._chk(self.prover.lib.glp_d2h(self.prover.ctx, self._roots.ctypes.data, self.roots_ptr(), 32 * B), "glp_d2h")
+        return [self._roots[t].tobytes() for t in range(len(self.counts))]
+
+    def proofs_arrays(self, queries=None, aunt_stride=None):
+        """(aunts uint8 [n][aunt_stride][32], n_aunts uint32 [n], leaf_hashes uint8 [n][32]) of the queries [(tree, leaf)], or of every leaf in
+        numbering order (queries=None): one launch (glp_tm_forest_proofs)"""
+        pr = self.prover
+        n = int(self.first[-1]) if queries is None else len(queries)
+        if aunt_stride is None:
+            aunt_stride = self.info()[2]
+        aunts, na, lh = np.zeros((n, aunt_stride, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros((n, 32), dtype=np.uint8)
+        qt = ql = None
+        if queries is not None:
+            qt, ql = np.array([q[0] for q in queries], dtype=np.uint64), np.array([q[1] for q in queries], dtype=np.uint64)
+        bufs = [pr.alloc(max(8, aunts.nbytes)), pr.alloc(max(8, na.nbytes)), pr.alloc(max(8, lh.nbytes))]
+        try:
+            pr._chk(pr.lib.glp_tm_forest_proofs(pr.ctx, self.handle, None if qt is None else qt.ctypes.data, None if ql is None else ql.ctypes.data, n,
+                                                bufs[0].ptr, aunt_stride, bufs[1].ptr, bufs[2].ptr), "glp_tm_forest_proofs")
+            self.proofs_counts = pr.tm_forest_last_counts()
+            if n:
+                if aunts.nbytes:
+                    aunts = bufs[0].download(aunts.shape, dtype=np.uint8)
+                na, lh = bufs[1].download(na.shape, dtype=np.uint32), bufs[2].download(lh.shape, dtype=np.uint8)
+        finally:
+            for b in bufs:
+                b.free()
+        return aunts, na, lh
+
+    def proofs(self, queries=None):
+        """the proofs (total, index, leaf_hash, aunts) of the queries [(tree, leaf)], or of every leaf in numbering order (queries=None)"""
+        aunts, na, lh = self.proofs_arrays(queries)
+        if queries is None:
+            queries = [(t, i) for t, c in enumerate(self.counts) for i in range(c)]
+        return [(self.counts[t], i, lh[q].tobytes(), [aunts[q, k].tobytes() for k in range(int(na[q]))]) for q, (t, i) in enumerate(queries)]
+
+    def free(self):
+        if self.handle is not None:
+            self.prover.lib.glp_tm_forest_destroy(self.handle)
+            self.handle = None
+            if self in self.prover._circuits:
+                self.prover._circuits.remove(self)
 
 
 class PlonkCircuit:

@@ -14,6 +14,7 @@ Everything here restates PUBLIC formats from memory, because the reference mount
 
 No CPU fallback: every hash and signature check below runs in the HIP kernels of libglprover.so.
 """
+import collections
 import struct
 
 import numpy as np
@@ -167,6 +168,55 @@ def data_commitment(prover, heights, data_roots) -> bytes:
     abi.encode(height, dataRoot) for every block of the range (DataCommitmentCircuit's witness)."""
     leaves = b"".join(encode_data_root_tuple(h, r) for h, r in zip(heights, data_roots))
     return prover.tm_merkle_root(leaves, 64)
+
+
+# ---- inclusion proofs (GPU) --------------------------------------------------------------------
+
+# BUILD-DEFINED: [RECALLED] Tendermint's crypto/merkle.Proof{Total, Index, LeafHash, Aunts}, restated from memory and unpinned — the aunts are the
+# sibling hashes bottom-up (nearest the leaf first), 32 bytes each; an odd last node of a level is promoted and contributes no aunt there.
+InclusionProof = collections.namedtuple("InclusionProof", "total index leaf_hash aunts")
+
+
+def _forest_proofs(prover, trees, queries):
+    forest = prover.tm_forest(trees)
+    try:
+        return forest.roots(), [InclusionProof(*p) for p in forest.proofs(queries)]
+    finally:
+        forest.free()
+
+
+def data_root_inclusion_proofs(prover, heights, data_roots, indices=None):
+    """(commitment, [InclusionProof]) of a block range: the data commitment (the root data_commitment gives) and the audit path of every
+    DataRootTuple of the range, or of the tuples `indices` — ONE forest build and one path launch on the device (glp_tm_forest_*).
+    [RECALLED] what Blobstream's verifyAttestation checks against the commitment."""
+    leaves = [encode_data_root_tuple(h, r) for h, r in zip(heights, data_roots)]
+    roots, proofs = _forest_proofs(prover, [leaves], None if indices is None else [(0, int(i)) for i in indices])
+    return roots[0], proofs
+
+
+def verify_data_root_inclusions(prover, commitment, heights, data_roots, proofs):
+    """the list form: status int32[n] (TM_INCLUSION_OK = 0 / BAD_SHAPE / BAD_ROOT) of proofs[k] for the tuple (heights[k], data_roots[k]) against
+    the commitment alone, in one launch.  The tuple's BYTES are hashed on the device; the proof's leaf_hash is not trusted."""
+    leaves = [encode_data_root_tuple(h, r) for h, r in zip(heights, data_roots)]
+    return prover.tm_verify_inclusion_batch([bytes(commitment)], proofs, leaves)
+
+
+def verify_data_root_inclusion(prover, commitment, height, data_root, proof) -> bool:
+    """True when `proof` places the tuple (height, data_root) inside `commitment`"""
+    return int(verify_data_root_inclusions(prover, commitment, [height], [data_root], [proof])[0]) == 0
+
+
+def validator_inclusion_proofs(prover, pubkeys, powers, indices=None):
+    """(validators hash, [InclusionProof]) of a validator set: membership proofs of every validator, or of `indices` (leaves of differing lengths)"""
+    leaves = [encode_validator(k, p) for k, p in zip(pubkeys, powers)]
+    roots, proofs = _forest_proofs(prover, [leaves], None if indices is None else [(0, int(i)) for i in indices])
+    return roots[0], proofs
+
+
+def header_field_proofs(prover, headers_fields, field_index):
+    """([header hash], [InclusionProof]) of B headers in ONE forest call: headers_fields[b] = the 14 field encodings of header b; proof b places
+    field `field_index` (6 = data_hash, 4 = last_block_id) inside header b's hash"""
+    return _forest_proofs(prover, [[bytes(x) for x in f] for f in headers_fields], [(b, int(field_index)) for b in range(len(headers_fields))])
 
 
 # ---- signatures and voting power ---------------------------------------------------------------

@@ -74,6 +74,8 @@ struct glp_ctx {
     // the same of the last glp_tm_merkle_root_batch and of the last glp_header_chain_leaf_inputs
     uint32_t tm_batch_counts[2] = {0, 0};
     uint32_t chain_input_counts[2] = {0, 0};
+    // the same of the last glp_tm_forest_create / glp_tm_forest_proofs / glp_tm_verify_inclusion_batch (glp_tm_forest_last_counts)
+    uint32_t tm_forest_counts[2] = {0, 0};
 };
 
 // stage timing tree of the prover drivers (the TimingTree of the upstream prover, recalled): a

@@ -560,6 +560,215 @@ extern "C" int glp_tm_merkle_root_batch_host(const uint8_t* data, uint64_t data_
     return GLP_OK;
 }
 
+// ---- trees with every level kept, audit paths, batched inclusion checks (tm_proof_kernels.cuh) ------------------------------------------------
+#include "tm_proof_kernels.cuh"
+static_assert(GLP_TM_INC_OK == GLP_TM_INCLUSION_OK && GLP_TM_INC_BAD_SHAPE == GLP_TM_INCLUSION_BAD_SHAPE && GLP_TM_INC_BAD_ROOT == GLP_TM_INCLUSION_BAD_ROOT &&
+              GLP_TM_FOREST_MAX_TREE == GLP_TM_FOREST_MAX_LEAVES, "glprover.h and tm_proof_kernels.cuh name the same codes");
+
+struct glp_tm_forest {
+    glp_ctx* c = nullptr;
+    void* block = nullptr;                   // one pool block: slab | roots | tree_first | upper_base
+    u32* slab = nullptr;
+    uint8_t* roots = nullptr;
+    u64 *d_tree_first = nullptr, *d_upper_base = nullptr;
+    std::vector<u64> tree_first;             // the checked host copy: what glp_tm_forest_proofs validates queries against
+    GlpTmForestPlan plan;
+    u64 n_trees = 0, total_leaves = 0, bytes = 0;
+};
+
+static void tm_forest_args(const glp_tm_forest* f, GlpTmForestArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.tree_first = f->d_tree_first; a.upper_base = f->d_upper_base; a.n_trees = f->n_trees; a.total_leaves = f->total_leaves;
+    a.slab = f->slab; a.roots = f->roots; a.k256 = f->c->hash->d_k256;
+}
+
+extern "C" int glp_tm_forest_create(glp_ctx* c, const uint8_t* d_data, uint64_t data_len, const uint64_t* h_leaf_offsets, const uint64_t* h_tree_first,
+                                    uint64_t total_leaves, uint64_t n_trees, uint8_t* h_roots, glp_tm_forest** out) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->tm_forest_counts[0] = c->tm_forest_counts[1] = 0;
+    if (!out) { glp_set_err(c, "glp_tm_forest_create: null argument"); return GLP_E_INVALID; }
+    if (n_trees && (!h_leaf_offsets || !h_tree_first || (!d_data && data_len))) { glp_set_err(c, "glp_tm_forest_create: null argument"); return GLP_E_INVALID; }
+    static const u64 none[1] = {0};
+    if (n_trees == 0) {                      // an empty forest: a handle that admits no query
+        if (total_leaves) { glp_set_err(c, "glp_tm_forest_create: leaves without a tree"); return GLP_E_INVALID; }
+        h_tree_first = none;
+    } else {
+        const int bad = glp_tm_forest_check(h_leaf_offsets, h_tree_first, total_leaves, n_trees, data_len);
+        if (bad == 1) { glp_set_err(c, "glp_tm_forest_create: offsets decrease, pass data_len, or the trees do not cover the leaves"); return GLP_E_INVALID; }
+        if (bad == 2) { glp_set_err(c, "glp_tm_forest_create: a tree has more than 2^24 leaves"); return GLP_E_UNSUPPORTED; }
+        if (n_trees > 0x7fffffffull || total_leaves > (1ull << 36)) { glp_set_err(c, "glp_tm_forest_create: too many trees or leaves"); return GLP_E_UNSUPPORTED; }
+    }
+    int rc = ensure_sha_tables(c);
+    if (rc) return rc;
+    glp_tm_forest* f = new glp_tm_forest;
+    f->c = c; f->n_trees = n_trees; f->total_leaves = total_leaves;
+    f->tree_first.assign(h_tree_first, h_tree_first + n_trees + 1);
+    glp_tm_forest_plan(f->tree_first.data(), n_trees, f->plan);
+    const size_t n_first = (size_t)n_trees + 1, n_off = (size_t)total_leaves + 1, n_lvl = f->plan.level_pre.size();
+    const size_t slab_bytes = (size_t)f->plan.total_nodes * 32, root_bytes = (size_t)n_trees * 32;
+    f->bytes = slab_bytes + root_bytes + 2 * n_first * 8;
+    GlpPoolBuf keep(c), arrays(c);           // arrays: the leaf offsets and the level prefixes, needed by this call's launches only
+    if (keep.alloc(f->bytes) != hipSuccess || arrays.alloc((n_off + n_lvl * n_first) * 8) != hipSuccess) { delete f; return GLP_E_NOMEM; }
+    f->slab = (u32*)keep.p;
+    f->roots = (uint8_t*)keep.p + slab_bytes;
+    f->d_tree_first = (u64*)(f->roots + root_bytes);
+    f->d_upper_base = f->d_tree_first + n_first;
+    hipError_t e = hipMemcpyAsync(f->d_tree_first, f->tree_first.data(), n_first * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_upper_base, f->plan.upper_base.data(), n_first * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_trees) e = hipMemcpyAsync(arrays.u(), h_leaf_offsets, n_off * 8, hipMemcpyHostToDevice, c->stream);
+    for (size_t l = 0; l < n_lvl && e == hipSuccess; l++)
+        e = hipMemcpyAsync(arrays.u() + n_off + l * n_first, f->plan.level_pre[l].data(), n_first * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_trees) {
+        GlpTmForestArgs a;
+        tm_forest_args(f, a);
+        if (total_leaves) {
+            GlpTmBatchArgs b;
+            memset(&b, 0, sizeof(b));
+            b.data = d_data; b.leaf_off = arrays.u(); b.tree_first = f->d_tree_first; b.n_trees = n_trees; b.total_leaves = total_leaves;
+            b.nodes = f->slab; b.roots = f->roots; b.k256 = a.k256;
+            hipLaunchKernelGGL(glp_tm_batch_leaf_kernel<0>, dim3((unsigned)((total_leaves + 255) / 256)), dim3(256), 0, c->stream, b);
+            c->tm_forest_counts[0]++;
+        }
+        for (size_t l = 0; l < n_lvl; l++) {
+            a.level = (u32)l;
+            a.level_pre = arrays.u() + n_off + l * n_first;
+            const u64 items = f->plan.level_pre[l][n_trees];
+            hipLaunchKernelGGL(glp_tm_forest_level_kernel<0>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c->stream, a);
+            c->tm_forest_counts[0]++;
+        }
+        a.level = f->plan.top_level;
+        a.level_pre = nullptr;
+        if (f->plan.top_width <= 2 * GLP_TM_BATCH_LANES_SMALL)
+            hipLaunchKernelGGL(glp_tm_forest_top_kernel<GLP_TM_BATCH_LANES_SMALL>, dim3((unsigned)n_trees), dim3(GLP_TM_BATCH_LANES_SMALL), 0, c->stream, a);
+        else
+            hipLaunchKernelGGL(glp_tm_forest_top_kernel<GLP_TM_BATCH_LANES>, dim3((unsigned)n_trees), dim3(GLP_TM_BATCH_LANES), 0, c->stream, a);
+        c->tm_forest_counts[0]++;
+        e = hipGetLastError();
+        if (e == hipSuccess && h_roots) {
+            e = hipMemcpyAsync(h_roots, f->roots, root_bytes, hipMemcpyDeviceToHost, c->stream);
+            c->tm_forest_counts[1] = 1;
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+    }
+    if (e != hipSuccess) { glp_set_err(c, "glp_tm_forest_create: %s", hipGetErrorString(e)); delete f; return GLP_E_HIP; }
+    f->block = keep.release();
+    *out = f;
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_forest_info(const glp_tm_forest* f, uint64_t* n_trees, uint64_t* total_leaves, uint32_t* max_aunts, uint64_t* bytes) {
+    if (!f) return GLP_E_INVALID;
+    if (n_trees) *n_trees = f->n_trees;
+    if (total_leaves) *total_leaves = f->total_leaves;
+    if (max_aunts) *max_aunts = f->plan.max_aunts;
+    if (bytes) *bytes = f->bytes;
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_forest_roots(const glp_tm_forest* f, const uint8_t** d_roots) {
+    if (!f || !d_roots) return GLP_E_INVALID;
+    *d_roots = f->roots;
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_forest_destroy(glp_tm_forest* f) {
+    if (!f) return GLP_OK;
+    if (f->block) glp_pool_release(f->c, f->block);      // stream-ordered reuse: work of the ctx's stream that still reads it comes first
+    delete f;
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_forest_proofs(glp_ctx* c, const glp_tm_forest* f, const uint64_t* h_query_tree, const uint64_t* h_query_leaf, uint64_t n_queries,
+                                    uint8_t* d_aunts, uint32_t aunt_stride, uint32_t* d_n_aunts, uint8_t* d_leaf_hashes) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->tm_forest_counts[0] = c->tm_forest_counts[1] = 0;
+    if (!f || f->c != c) { glp_set_err(c, "glp_tm_forest_proofs: not a forest of this ctx"); return GLP_E_INVALID; }
+    if (glp_tm_forest_check_queries(f->tree_first.data(), f->n_trees, f->plan.max_aunts, h_query_tree, h_query_leaf, n_queries, aunt_stride)) {
+        glp_set_err(c, "glp_tm_forest_proofs: a query names no leaf of the forest, or aunt_stride is below the aunts of a queried tree");
+        return GLP_E_INVALID;
+    }
+    if (n_queries == 0) return GLP_OK;
+    if (!d_n_aunts || (!d_aunts && aunt_stride)) { glp_set_err(c, "glp_tm_forest_proofs: null argument"); return GLP_E_INVALID; }
+    if (n_queries > (1ull << 36)) { glp_set_err(c, "glp_tm_forest_proofs: too many queries"); return GLP_E_UNSUPPORTED; }
+    GlpPoolBuf q(c);
+    GlpTmPathArgs a;
+    memset(&a, 0, sizeof(a));
+    tm_forest_args(f, a.f);
+    if (h_query_tree) {
+        if (q.alloc((size_t)n_queries * 16) != hipSuccess) return GLP_E_NOMEM;
+        GLP_HIPCHK(c, hipMemcpyAsync(q.u(), h_query_tree, (size_t)n_queries * 8, hipMemcpyHostToDevice, c->stream));
+        GLP_HIPCHK(c, hipMemcpyAsync(q.u() + n_queries, h_query_leaf, (size_t)n_queries * 8, hipMemcpyHostToDevice, c->stream));
+        a.query_tree = q.u(); a.query_leaf = q.u() + n_queries;
+    }
+    a.n_queries = n_queries; a.aunts = d_aunts; a.n_aunts = d_n_aunts; a.leaf_hash = d_leaf_hashes; a.aunt_stride = aunt_stride;
+    hipLaunchKernelGGL(glp_tm_path_kernel<0>, dim3((unsigned)((n_queries + 255) / 256)), dim3(256), 0, c->stream, a);
+    c->tm_forest_counts[0] = 1;
+    GLP_HIPCHK(c, hipGetLastError());
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_verify_inclusion_batch(glp_ctx* c, const uint8_t* d_roots, uint64_t n_roots, const uint32_t* h_root_of, const uint8_t* d_data,
+                                             uint64_t data_len, const uint64_t* h_leaf_offsets, const uint64_t* d_index, const uint64_t* d_total,
+                                             const uint8_t* d_aunts, uint32_t aunt_stride, const uint32_t* d_n_aunts, uint64_t n, int32_t* h_status) {
+    if (!c) return GLP_E_INVALID;
+    GLP_BIND(c);
+    c->tm_forest_counts[0] = c->tm_forest_counts[1] = 0;
+    if (n == 0) return GLP_OK;
+    if (!d_roots || !h_leaf_offsets || !d_index || !d_total || !d_n_aunts || !h_status || (!d_data && data_len) || (!d_aunts && aunt_stride)) {
+        glp_set_err(c, "glp_tm_verify_inclusion_batch: null argument");
+        return GLP_E_INVALID;
+    }
+    if (glp_tm_verify_check(h_leaf_offsets, n, data_len, h_root_of, n_roots)) {
+        glp_set_err(c, "glp_tm_verify_inclusion_batch: offsets decrease or pass data_len, or a proof names no root");
+        return GLP_E_INVALID;
+    }
+    if (n > (1ull << 36)) { glp_set_err(c, "glp_tm_verify_inclusion_batch: too many proofs"); return GLP_E_UNSUPPORTED; }
+    int rc = ensure_sha_tables(c);
+    if (rc) return rc;
+    GlpPoolBuf arrays(c), stat(c);
+    const size_t n_off = (size_t)n + 1;
+    if (arrays.alloc(n_off * 8 + (h_root_of ? (size_t)n * 4 : 0)) != hipSuccess || stat.alloc((size_t)n * sizeof(int32_t)) != hipSuccess) return GLP_E_NOMEM;
+    GLP_HIPCHK(c, hipMemcpyAsync(arrays.u(), h_leaf_offsets, n_off * 8, hipMemcpyHostToDevice, c->stream));
+    if (h_root_of) GLP_HIPCHK(c, hipMemcpyAsync(arrays.u() + n_off, h_root_of, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    GlpTmVerifyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.roots = d_roots; a.root_of = h_root_of ? (const u32*)(arrays.u() + n_off) : nullptr; a.data = d_data; a.leaf_off = arrays.u();
+    a.index = d_index; a.total = d_total; a.aunts = d_aunts; a.n_aunts = d_n_aunts; a.n = n; a.status = (int32_t*)stat.p;
+    a.k256 = c->hash->d_k256; a.aunt_stride = aunt_stride;
+    hipLaunchKernelGGL(glp_tm_verify_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, a);
+    c->tm_forest_counts[0] = 1;
+    GLP_HIPCHK(c, hipGetLastError());
+    GLP_HIPCHK(c, hipMemcpyAsync(h_status, stat.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    c->tm_forest_counts[1] = 1;
+    GLP_HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_forest_last_counts(glp_ctx* c, uint32_t* n_launches, uint32_t* n_host_syncs) {
+    if (!c || !n_launches || !n_host_syncs) return GLP_E_INVALID;
+    *n_launches = c->tm_forest_counts[0];
+    *n_host_syncs = c->tm_forest_counts[1];
+    return GLP_OK;
+}
+
+extern "C" int glp_tm_forest_proofs_host(const uint8_t* data, uint64_t data_len, const uint64_t* leaf_offsets, const uint64_t* tree_first,
+                                         uint64_t total_leaves, uint64_t n_trees, const uint64_t* query_tree, const uint64_t* query_leaf,
+                                         uint64_t n_queries, uint8_t* roots, uint8_t* aunts, uint32_t aunt_stride, uint32_t* n_aunts,
+                                         uint8_t* leaf_hashes) {
+    const int bad = glp_tm_forest_proofs_host_impl(data, data_len, leaf_offsets, tree_first, total_leaves, n_trees, query_tree, query_leaf, n_queries,
+                                                   roots, aunts, aunt_stride, n_aunts, leaf_hashes, K256);
+    return bad == 0 ? GLP_OK : bad == 1 ? GLP_E_INVALID : GLP_E_UNSUPPORTED;
+}
+
+extern "C" int glp_tm_verify_inclusion_batch_host(const uint8_t* roots, uint64_t n_roots, const uint32_t* root_of, const uint8_t* data,
+                                                  uint64_t data_len, const uint64_t* leaf_offsets, const uint64_t* index, const uint64_t* total,
+                                                  const uint8_t* aunts, uint32_t aunt_stride, const uint32_t* n_aunts, uint64_t n, int32_t* status) {
+    return glp_tm_verify_inclusion_host_impl(roots, n_roots, root_of, data, data_len, leaf_offsets, index, total, aunts, aunt_stride, n_aunts, n,
+                                             status, K256) ? GLP_E_INVALID : GLP_OK;
+}
+
 extern "C" int glp_header_chain_leaf_input_words(const glp_header_chain_layout* layout, uint64_t* n_words) {
     if (!layout || !n_words) return GLP_E_INVALID;
     const u64 per = glp_chain_words_per_header(layout->field_len, layout->leaf_headers, layout->n_groups);

@@ -514,7 +514,9 @@ class DataCommitmentMapReduce:
                 "record_seconds": dict(self.record_seconds),
                 "commitment": b"".join(struct.pack(">I", v) for v in public[:8]) if root is not None else None}
 
-    def prove_range(self, heights, data_roots):
+    def prove_range(self, heights, data_roots, inclusion=False):
+        """inclusion=True: the result also carries "inclusion", one blobstream.InclusionProof per tuple of the range (one forest call on the
+        device, blobstream.data_root_inclusion_proofs), whose root must be the proven commitment.  The default result is untouched."""
         n = len(heights)
         if n % self.leaf_blocks or len(data_roots) != n:
             raise ValueError("the range is not a whole number of leaves")
@@ -527,9 +529,15 @@ class DataCommitmentMapReduce:
         else:
             root_proof, public, key, _ = self.reduce(leaves, levels)
         t2 = time.perf_counter()
-        return {"root_proof": root_proof, "public": public, "key": key, "leaves": len(leaves), "map_seconds": round(t1 - t0, 4),
-                "reduce_seconds": round(t2 - t1, 4), "levels": levels, "record_seconds": dict(self.record_seconds),
-                "commitment": b"".join(struct.pack(">I", v) for v in public[:8])}
+        out = {"root_proof": root_proof, "public": public, "key": key, "leaves": len(leaves), "map_seconds": round(t1 - t0, 4),
+               "reduce_seconds": round(t2 - t1, 4), "levels": levels, "record_seconds": dict(self.record_seconds),
+               "commitment": b"".join(struct.pack(">I", v) for v in public[:8])}
+        if inclusion:
+            bsm = importlib.import_module(__package__ + ".blobstream")
+            root, out["inclusion"] = bsm.data_root_inclusion_proofs(self.prover, heights, data_roots)
+            if root != out["commitment"]:
+                raise RuntimeError("the inclusion forest's root is not the proven commitment")
+        return out
 
     def expected_key(self, n_blocks):
         """The VERIFIER's own setup: the verifying key of the root circuit for a range of n_blocks, derived on THIS object from a synthetic range

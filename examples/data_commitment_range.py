@@ -29,7 +29,7 @@ data_roots = [rng.integers(0, 256, 32, dtype=np.uint8).tobytes() for _ in height
 mr = dm.DataCommitmentMapReduce(provers[0], consts, leaf_blocks=64, fan_in=8, map_provers=provers[1:])
 for label in ("first run (records the circuits)", "second run"):
     t0 = time.perf_counter()
-    out = mr.prove_range(heights, data_roots)
+    out = mr.prove_range(heights, data_roots, inclusion=True)
     print(f"{label}: {time.perf_counter() - t0:.2f} s  (map {out['map_seconds']} s, reduce {out['reduce_seconds']} s, proof {len(out['root_proof'])} bytes)")
 
 # the consumer: knows the tuples, holds the root proof and the root circuit's key — nothing else
@@ -39,6 +39,13 @@ while len(level) > 1:
 assert out["commitment"] == level[0], "the proof's commitment is the RFC 6962 root of the tuples"
 assert mr.verify(out["root_proof"], out["key"], heights, data_roots, out["commitment"])
 print("commitment", out["commitment"].hex(), "verified")
+
+# another consumer: holds ONE tuple, its inclusion proof and the proven commitment — not the range
+bs = importlib.import_module(graft.PKG_NAME + ".blobstream")
+k = blocks // 3
+assert bs.verify_data_root_inclusion(provers[0], out["commitment"], heights[k], data_roots[k], out["inclusion"][k])
+assert not bs.verify_data_root_inclusion(provers[0], out["commitment"], heights[k] + 1, data_roots[k], out["inclusion"][k])
+print(f"block {heights[k]}: its data root lies inside the commitment ({len(out['inclusion'][k].aunts)} aunts)")
 mr.free()
 for p in provers:
     p.close()

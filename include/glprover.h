@@ -735,6 +735,57 @@ int glp_tm_merkle_root_batch_last_counts(glp_ctx* ctx, uint32_t* n_launches, uin
 int glp_tm_merkle_root_batch_host(const uint8_t* data, uint64_t data_len, const uint64_t* leaf_offsets, const uint64_t* tree_first,
                                   uint64_t total_leaves, uint64_t n_trees, uint8_t* roots);
 
+/* INCLUSION PROOFS: the same trees with EVERY LEVEL KEPT on the device, the audit paths of any leaves read out of them, and the batched check
+ * of such paths against roots — "this DataRootTuple lies inside the proven data commitment", validator-set membership, "this field belongs to
+ * this header hash".  The proof format is BUILD-DEFINED (Tendermint's crypto/merkle.Proof{Total, Index, LeafHash, Aunts} restated from memory,
+ * unpinned): the proof of leaf `index` of `total` leaves is its sibling hashes BOTTOM-UP (nearest the leaf first), 32 bytes each; leaf hash
+ * SHA256(00 || leaf), inner hash SHA256(01 || l || r); an odd last node of a level is promoted and contributes NO aunt at that level, so the
+ * aunt count is fixed by (index, total) and is at most ceil(log2 total): with 5 leaves, leaf 4 has 1 aunt and leaf 0 has 3.
+ * glp_tm_forest_create: arguments as glp_tm_merkle_root_batch (arrays validated on the host before anything is launched; on a refusal nothing
+ *   is written and no handle is made), with at most GLP_TM_FOREST_MAX_LEAVES leaves per tree (GLP_E_UNSUPPORTED above).  At most
+ *   2 + max(0, ceil(log2(largest tree)) - 9) launches — leaf hashes, one launch per level while the widest tree has more than 512 nodes, one
+ *   workgroup per tree for the rest — and NO synchronise, unless h_roots [n_trees][32] is not NULL: then one copy and one synchronise.  d_data
+ *   and h_leaf_offsets are not needed once the stream has passed the call.  n_trees == 0 is GLP_OK (a forest that admits no query); a tree
+ *   without leaves has the root SHA256("") and admits no query.  The forest belongs to ctx: use it on that ctx, destroy it before the ctx.
+ * glp_tm_forest_info: trees, leaves, the aunts of leaf 0 of the largest tree (max_aunts), device bytes held; any pointer may be NULL.
+ * glp_tm_forest_roots: the device array [n_trees][32], valid until the forest is destroyed.
+ * glp_tm_forest_proofs: ONE launch and no synchronise for any number of queries (h_query_tree[q], h_query_leaf[q] = leaf inside that tree),
+ *   validated on the host before the launch: tree < n_trees, leaf < that tree's count, aunt_stride >= ceil(log2(count)) of every queried tree —
+ *   GLP_E_INVALID otherwise, nothing written.  Both arrays NULL with n_queries == total_leaves: every leaf in numbering order.  Writes
+ *   d_aunts [n_queries][aunt_stride][32] (slots past a row's count are written as ZERO), d_n_aunts [n_queries], and d_leaf_hashes
+ *   [n_queries][32] unless NULL.  The host arrays must stay until the stream has passed the call.
+ * glp_tm_verify_inclusion_batch: n proofs in ONE launch and one synchronise (after the copy to h_status [n]): proof p is leaf BYTES
+ *   d_data[h_leaf_offsets[p] .. h_leaf_offsets[p + 1]) — hashed here with the 00 prefix, never a leaf hash taken from the proof — d_index[p],
+ *   d_total[p], d_n_aunts[p] and row p of d_aunts, against root h_root_of[p] (NULL: root 0) of d_roots [n_roots][32].  index, total and n_aunts
+ *   are untrusted: GLP_TM_INCLUSION_BAD_SHAPE for total == 0, index >= total, n_aunts > aunt_stride or n_aunts not the count (index, total)
+ *   fixes (no aunt is read then); else GLP_TM_INCLUSION_BAD_ROOT or GLP_TM_INCLUSION_OK.  The offsets and h_root_of are checked on the host
+ *   (GLP_E_INVALID).  n == 0 is GLP_OK.
+ * glp_tm_forest_last_counts: launches and synchronises of the LAST of these three calls on the ctx.
+ * The _host forms run the same per-item functions serially; no ctx, no GPU.  glp_tm_forest_proofs_host builds the trees and reads the paths in
+ * one call (roots [n_trees][32] may be NULL). */
+#define GLP_TM_FOREST_MAX_LEAVES (1ull << 24)
+#define GLP_TM_INCLUSION_OK 0
+#define GLP_TM_INCLUSION_BAD_SHAPE 1
+#define GLP_TM_INCLUSION_BAD_ROOT 2
+typedef struct glp_tm_forest glp_tm_forest;
+int glp_tm_forest_create(glp_ctx* ctx, const uint8_t* d_data, uint64_t data_len, const uint64_t* h_leaf_offsets, const uint64_t* h_tree_first,
+                         uint64_t total_leaves, uint64_t n_trees, uint8_t* h_roots, glp_tm_forest** out);
+int glp_tm_forest_info(const glp_tm_forest* forest, uint64_t* n_trees, uint64_t* total_leaves, uint32_t* max_aunts, uint64_t* bytes);
+int glp_tm_forest_roots(const glp_tm_forest* forest, const uint8_t** d_roots);
+int glp_tm_forest_destroy(glp_tm_forest* forest);
+int glp_tm_forest_proofs(glp_ctx* ctx, const glp_tm_forest* forest, const uint64_t* h_query_tree, const uint64_t* h_query_leaf, uint64_t n_queries,
+                         uint8_t* d_aunts, uint32_t aunt_stride, uint32_t* d_n_aunts, uint8_t* d_leaf_hashes);
+int glp_tm_verify_inclusion_batch(glp_ctx* ctx, const uint8_t* d_roots, uint64_t n_roots, const uint32_t* h_root_of, const uint8_t* d_data,
+                                  uint64_t data_len, const uint64_t* h_leaf_offsets, const uint64_t* d_index, const uint64_t* d_total,
+                                  const uint8_t* d_aunts, uint32_t aunt_stride, const uint32_t* d_n_aunts, uint64_t n, int32_t* h_status);
+int glp_tm_forest_last_counts(glp_ctx* ctx, uint32_t* n_launches, uint32_t* n_host_syncs);
+int glp_tm_forest_proofs_host(const uint8_t* data, uint64_t data_len, const uint64_t* leaf_offsets, const uint64_t* tree_first,
+                              uint64_t total_leaves, uint64_t n_trees, const uint64_t* query_tree, const uint64_t* query_leaf, uint64_t n_queries,
+                              uint8_t* roots, uint8_t* aunts, uint32_t aunt_stride, uint32_t* n_aunts, uint8_t* leaf_hashes);
+int glp_tm_verify_inclusion_batch_host(const uint8_t* roots, uint64_t n_roots, const uint32_t* root_of, const uint8_t* data, uint64_t data_len,
+                                       const uint64_t* leaf_offsets, const uint64_t* index, const uint64_t* total, const uint8_t* aunts,
+                                       uint32_t aunt_stride, const uint32_t* n_aunts, uint64_t n, int32_t* status);
+
 /* The INPUT VECTORS of the header-chain leaf on the device: from the raw headers of a chain to the rows glp_witness_eval_device reads.
  * d_headers: n headers, each the concatenation of its 14 field encodings at the layout's lengths (field_len: what the leaf recording fixes;
  * leaf_headers: headers per leaf; n_groups: the varint bytes of a height).  Three steps, at most 4 launches and ONE synchronise (after the
