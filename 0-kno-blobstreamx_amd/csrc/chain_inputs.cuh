@@ -1,4 +1,4 @@
-// chain_inputs.cuh — the header-chain leaf's INPUT VECTORS on the device (glp_header_chain_leaf_inputs, hash.hip): from the raw headers of a
+// chain_inputs.cuh — the header-chain leaf's INPUT VECTORS on the device (glp_header_chain_leaf_inputs, tm.hip): from the raw headers of a
 // chain (each the concatenation of its 14 field encodings at the layout's lengths) to the rows glp_witness_eval_device reads, word for word
 // what data_commitment_mr._chain_leaf_inputs builds, after the tests of data_commitment_mr.HeaderChainMapReduce._map_chain.  After the header
 // hashes (tm_batch_kernels.cuh, uniform form: n trees of 14 leaves) two kernels:
@@ -143,6 +143,14 @@ static inline int glp_header_chain_fill_args(GlpChainArgs& a, GlpTmBatchArgs& t,
     t.roots = hashes + 32; t.k256 = k256; t.uni_leaves = GLP_CHAIN_FIELDS; t.uni_stride = a.pre[GLP_CHAIN_FIELDS];
     for (int j = 0; j <= GLP_TM_UNIFORM_MAX; j++) t.uni_pre[j] = j <= GLP_CHAIN_FIELDS ? a.pre[j] : 0;
     return 0;
+}
+
+// The launches of the call, written once for the driver (tm.hip, l = GlpLaunch, device pointers in a and t) and the CPU emulation
+// (l = GlpEmuLaunch, host pointers): the header hashes (t: a.n trees of 14 leaves, uniform form), the tests, the rows.
+template <class L> static inline void glp_header_chain_launches(L& l, const GlpChainArgs& a, const GlpTmBatchArgs& t) {
+    glp_tm_batch_launches(l, t, GLP_CHAIN_FIELDS);
+    l.launch(glp_header_chain_check_kernel<0>, (a.n + 255) / 256, 256, a);
+    l.launch(glp_header_chain_rows_kernel<0>, a.n, 64, a);
 }
 
 static inline int glp_header_chain_leaf_inputs_host_impl(const u32* field_len, u32 leaf_headers, u32 n_groups, const uint8_t* headers,

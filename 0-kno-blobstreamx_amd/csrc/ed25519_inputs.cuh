@@ -374,3 +374,19 @@ __global__ void __launch_bounds__(64) glp_ed25519_leaf_inputs_kernel(const GlpEd
         glp_put_limbs24<7>(q2, row + o); o += 7;
     }
 }
+
+// The launches of the calls, written once for the driver (tm.hip, l = GlpLaunch, device pointers) and the CPU emulation (l = GlpEmuLaunch, host
+// pointers): one work-item per slot, 64 per workgroup
+template <class L>
+static inline void glp_ed25519_witness_launch(L& l, const uint8_t* pubs, const uint8_t* sigs, const uint8_t* msgs, u32 msg_stride, const u32* lens,
+                                              u64 n, const u64* k512, u64* out) {
+    l.launch(glp_ed25519_witness_kernel<0>, (n + 63) / 64, 64, pubs, sigs, msgs, msg_stride, lens, n, k512, out);
+}
+template <class L> static inline void glp_ed25519_half_scalars_launch(L& l, const u64* ks, u64 n, u64* out) {
+    l.launch(glp_ed25519_half_scalars_kernel<0>, (n + 63) / 64, 64, ks, n, out);
+}
+// the witness kernel over the slots' own triples into recs (= a.recs, writable), then the input kernel
+template <class L> static inline void glp_ed25519_leaf_inputs_launches(L& l, const GlpEdInputsArgs& a, u64* recs) {
+    glp_ed25519_witness_launch(l, a.pubs, a.sigs, a.msgs, a.msg_stride, a.lens, a.n, a.k512, recs);
+    l.launch(glp_ed25519_leaf_inputs_kernel<0>, (a.n + 63) / 64, 64, a);
+}

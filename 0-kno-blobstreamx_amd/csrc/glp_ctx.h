@@ -112,6 +112,18 @@ struct GlpPoolBuf {
     void* release() { void* q = p; p = nullptr; return q; }
     u64* u() const { return (u64*)p; }
 };
+// How a driver issues a kernel: a 1-D grid and block on the ctx's stream, every launch counted in *n (the launch half of a *_counts pair).
+// The launch sequences beside the kernels are templates over this type, and the CPU emulation runs them through its own form of it
+// (GlpEmuLaunch, tests/emu/hip_emu.h).  launch_sync is for kernels with barriers or shuffles: the same here, real threads there.
+struct GlpLaunch {
+    glp_ctx* c;
+    uint32_t* n;
+    template <class K, class... A> void launch(K kernel, u64 grid, unsigned block, const A&... args) const {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, c->stream, args...);
+        ++*n;
+    }
+    template <class K, class... A> void launch_sync(K kernel, u64 grid, unsigned block, const A&... args) const { launch(kernel, grid, block, args...); }
+};
 void glp_hash_destroy(glp_ctx* c);
 
 // HIP's current device is a per-host-thread setting and a ctx may be driven from a worker thread (MapReduce map

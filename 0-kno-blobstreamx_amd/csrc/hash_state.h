@@ -1,4 +1,4 @@
-// hash_state.h — per-context hashing state shared by hash.hip and fri.hip (internal).
+// hash_state.h — per-context hashing state shared by hash.hip, fri.hip and tm.hip (internal).
 #pragma once
 #include <vector>
 #include "glp_ctx.h"
@@ -17,6 +17,11 @@ struct glp_hash_state {
     u64* d_k512 = nullptr;
 };
 glp_hash_state* glp_hash_get(glp_ctx* c);
+// the SHA-256 / SHA-512 round constants, defined once (hash.hip), and their upload into d_k256 / d_k512 on a ctx's first use; hidden, so the
+// library's dynamic symbols stay what they were when these were file-local
+__attribute__((visibility("hidden"))) extern const u32 glp_k256[64];
+__attribute__((visibility("hidden"))) extern const u64 glp_k512[80];
+__attribute__((visibility("hidden"))) int glp_ensure_sha_tables(glp_ctx* c);
 static inline GlpPoseidonConsts glp_dev_consts(const glp_hash_state* h) {
     return GlpPoseidonConsts{h->d_consts, h->d_consts + 360, h->d_consts + 372, h->d_pg_coef, h->d_pg_cst};
 }

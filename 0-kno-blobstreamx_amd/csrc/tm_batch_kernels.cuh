@@ -1,5 +1,5 @@
 // tm_batch_kernels.cuh — B Tendermint "simple" Merkle trees (RFC 6962 prefixes) per call: glp_tm_merkle_root_batch and the header hashes of
-// glp_header_chain_leaf_inputs (hash.hip).  Two kernels, both 1-D grids:
+// glp_header_chain_leaf_inputs (tm.hip).  Two kernels, both 1-D grids:
 //   glp_tm_batch_leaf_kernel   one work-item per leaf over ALL trees: nodes[i] = SHA256(00 || leaf i), streamed block by block, any length
 //   glp_tm_batch_fold_kernel   one workgroup of LANES lanes per tree (tree = blockIdx.x): level 0 pairs the leaf hashes straight from global
 //                              memory, every later level folds in place in 32 * LANES bytes of LDS (01 || l || r, an odd last node promoted
@@ -171,8 +171,9 @@ __global__ void __launch_bounds__(LANES) glp_tm_batch_fold_kernel(const GlpTmBat
 }
 
 // ---- what the host checks before a launch, and the host form --------------------------------------------------------------------------------
-// 0 = the arrays are sound; 1 = not (GLP_E_INVALID); 2 = a tree has more than GLP_TM_BATCH_MAX_LEAVES leaves (GLP_E_UNSUPPORTED)
-static inline int glp_tm_batch_check(const u64* leaf_off, const u64* tree_first, u64 total_leaves, u64 n_trees, u64 data_len) {
+// 0 = the arrays are sound; 1 = not (GLP_E_INVALID); 2 = a tree has more than max_tree leaves (GLP_E_UNSUPPORTED)
+static inline int glp_tm_batch_check(const u64* leaf_off, const u64* tree_first, u64 total_leaves, u64 n_trees, u64 data_len,
+                                     u64 max_tree = GLP_TM_BATCH_MAX_LEAVES) {
     if (tree_first[0] != 0 || tree_first[n_trees] != total_leaves) return 1;
     for (u64 t = 0; t < n_trees; t++)
         if (tree_first[t] > tree_first[t + 1]) return 1;
@@ -180,8 +181,22 @@ static inline int glp_tm_batch_check(const u64* leaf_off, const u64* tree_first,
     for (u64 i = 0; i < total_leaves; i++)
         if (leaf_off[i] > leaf_off[i + 1]) return 1;
     for (u64 t = 0; t < n_trees; t++)
-        if (tree_first[t + 1] - tree_first[t] > GLP_TM_BATCH_MAX_LEAVES) return 2;
+        if (tree_first[t + 1] - tree_first[t] > max_tree) return 2;
     return 0;
+}
+
+static inline u64 glp_tm_batch_max_tree(const u64* tree_first, u64 n_trees) {
+    u64 m = 0;
+    for (u64 t = 0; t < n_trees; t++) m = tree_first[t + 1] - tree_first[t] > m ? tree_first[t + 1] - tree_first[t] : m;
+    return m;
+}
+
+// The launches of a call, written once for the driver (tm.hip, l = GlpLaunch, device pointers in a) and the CPU emulation (l = GlpEmuLaunch,
+// host pointers): the leaves, then the fold over a.n_trees (> 0) trees none of which has more than max_tree leaves.
+template <class L> static inline void glp_tm_batch_launches(L& l, const GlpTmBatchArgs& a, u64 max_tree) {
+    if (a.total_leaves) l.launch(glp_tm_batch_leaf_kernel<0>, (a.total_leaves + 255) / 256, 256, a);
+    if (max_tree <= 2 * GLP_TM_BATCH_LANES_SMALL) l.launch_sync(glp_tm_batch_fold_kernel<GLP_TM_BATCH_LANES_SMALL>, a.n_trees, GLP_TM_BATCH_LANES_SMALL, a);
+    else l.launch_sync(glp_tm_batch_fold_kernel<GLP_TM_BATCH_LANES>, a.n_trees, GLP_TM_BATCH_LANES, a);
 }
 
 // tree t of `a` serially, with the functions the kernels call; scratch: 8 * (the tree's leaves) words

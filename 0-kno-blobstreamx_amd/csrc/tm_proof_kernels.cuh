@@ -1,5 +1,5 @@
 // tm_proof_kernels.cuh — Tendermint "simple" Merkle trees (RFC 6962 prefixes) with EVERY LEVEL KEPT, the audit paths read out of them and the
-// batched check of such paths: glp_tm_forest_create / glp_tm_forest_proofs / glp_tm_verify_inclusion_batch (hash.hip).  The proof format is
+// batched check of such paths: glp_tm_forest_create / glp_tm_forest_proofs / glp_tm_verify_inclusion_batch (tm.hip).  The proof format is
 // BUILD-DEFINED (a restatement from memory of Tendermint's crypto/merkle.Proof{Total, Index, LeafHash, Aunts}, unpinned): the aunts of leaf i
 // are its sibling hashes bottom-up, 32 bytes each; an odd last node of a level is promoted and contributes no aunt there.
 // The slab (node = 8 big-endian words):
@@ -245,15 +245,7 @@ __global__ void __launch_bounds__(256) glp_tm_verify_kernel(const GlpTmVerifyArg
 // ---- what the host checks and plans before a launch, and the host forms ---------------------------------------------------------------------
 // 0 = the arrays are sound; 1 = not (GLP_E_INVALID); 2 = a tree has more than GLP_TM_FOREST_MAX_TREE leaves (GLP_E_UNSUPPORTED)
 static inline int glp_tm_forest_check(const u64* leaf_off, const u64* tree_first, u64 total_leaves, u64 n_trees, u64 data_len) {
-    if (tree_first[0] != 0 || tree_first[n_trees] != total_leaves) return 1;
-    for (u64 t = 0; t < n_trees; t++)
-        if (tree_first[t] > tree_first[t + 1]) return 1;
-    if (leaf_off[total_leaves] > data_len) return 1;
-    for (u64 i = 0; i < total_leaves; i++)
-        if (leaf_off[i] > leaf_off[i + 1]) return 1;
-    for (u64 t = 0; t < n_trees; t++)
-        if (tree_first[t + 1] - tree_first[t] > GLP_TM_FOREST_MAX_TREE) return 2;
-    return 0;
+    return glp_tm_batch_check(leaf_off, tree_first, total_leaves, n_trees, data_len, GLP_TM_FOREST_MAX_TREE);
 }
 
 struct GlpTmForestPlan {
@@ -307,6 +299,33 @@ static inline int glp_tm_verify_check(const u64* leaf_off, u64 n, u64 data_len, 
     return 0;
 }
 
+// what the leaf-hash kernel is given to fill level 0 of forest a: the slab's leaf region is its node array
+static inline GlpTmBatchArgs glp_tm_forest_leaf_args(const GlpTmForestArgs& a, const uint8_t* data, const u64* leaf_off) {
+    GlpTmBatchArgs b;
+    memset(&b, 0, sizeof(b));
+    b.data = data; b.leaf_off = leaf_off; b.tree_first = a.tree_first; b.n_trees = a.n_trees; b.total_leaves = a.total_leaves; b.nodes = a.slab;
+    b.roots = a.roots; b.k256 = a.k256;
+    return b;
+}
+
+// The launches of the three calls, written once for the driver (tm.hip, l = GlpLaunch, device pointers) and the CPU emulation (l = GlpEmuLaunch,
+// host pointers).  A forest of a.n_trees > 0 trees: the leaves, a level launch per entry of plan.level_pre (level_pre(i): where the kernel reads it), the top.
+template <class L, class Pre>
+static inline void glp_tm_forest_create_launches(L& l, GlpTmForestArgs a, const GlpTmBatchArgs& leaves, const GlpTmForestPlan& plan, Pre level_pre) {
+    if (a.total_leaves) l.launch(glp_tm_batch_leaf_kernel<0>, (a.total_leaves + 255) / 256, 256, leaves);
+    for (size_t i = 0; i < plan.level_pre.size(); i++) {
+        a.level = (u32)i;
+        a.level_pre = level_pre(i);
+        l.launch(glp_tm_forest_level_kernel<0>, (plan.level_pre[i][a.n_trees] + 255) / 256, 256, a);
+    }
+    a.level = plan.top_level;
+    a.level_pre = nullptr;
+    if (plan.top_width <= 2 * GLP_TM_BATCH_LANES_SMALL) l.launch_sync(glp_tm_forest_top_kernel<GLP_TM_BATCH_LANES_SMALL>, a.n_trees, GLP_TM_BATCH_LANES_SMALL, a);
+    else l.launch_sync(glp_tm_forest_top_kernel<GLP_TM_BATCH_LANES>, a.n_trees, GLP_TM_BATCH_LANES, a);
+}
+template <class L> static inline void glp_tm_path_launch(L& l, const GlpTmPathArgs& a) { l.launch(glp_tm_path_kernel<0>, (a.n_queries + 255) / 256, 256, a); }
+template <class L> static inline void glp_tm_verify_launch(L& l, const GlpTmVerifyArgs& a) { l.launch(glp_tm_verify_kernel<0>, (a.n + 255) / 256, 256, a); }
+
 // the whole forest serially, with the functions the kernels call; slab: plan.total_nodes * 8 words
 static inline void glp_tm_forest_build_host(const GlpTmBatchArgs& leaves, const GlpTmForestArgs& a) {
     for (u64 i = 0; i < a.total_leaves; i++) glp_tm_batch_leaf_item(leaves, i);
@@ -343,15 +362,11 @@ static inline int glp_tm_forest_proofs_host_impl(const uint8_t* data, u64 data_l
     std::vector<u32> slab((size_t)plan.total_nodes * 8);
     std::vector<uint8_t> own_roots;
     if (!roots) { own_roots.resize((size_t)n_trees * 32); roots = own_roots.data(); }
-    GlpTmBatchArgs b;
-    memset(&b, 0, sizeof(b));
-    b.data = data; b.leaf_off = leaf_offsets; b.tree_first = tree_first; b.n_trees = n_trees; b.total_leaves = total_leaves; b.nodes = slab.data();
-    b.roots = roots; b.k256 = k256;
     GlpTmPathArgs a;
     memset(&a, 0, sizeof(a));
     a.f.tree_first = tree_first; a.f.upper_base = plan.upper_base.data(); a.f.n_trees = n_trees; a.f.total_leaves = total_leaves;
     a.f.slab = slab.data(); a.f.roots = roots; a.f.k256 = k256;
-    glp_tm_forest_build_host(b, a.f);
+    glp_tm_forest_build_host(glp_tm_forest_leaf_args(a.f, data, leaf_offsets), a.f);
     a.query_tree = query_tree; a.query_leaf = query_leaf; a.n_queries = n_queries; a.aunts = aunts; a.n_aunts = n_aunts; a.leaf_hash = leaf_hashes;
     a.aunt_stride = aunt_stride;
     for (u64 q = 0; q < n_queries; q++) glp_tm_path_item(a, q);

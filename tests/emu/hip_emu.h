@@ -93,3 +93,26 @@ inline void glp_emu_launch(unsigned grid, unsigned block, size_t lds_bytes, cons
     glp_emu::block_barrier = nullptr;
     glp_emu::dyn_lds = nullptr;
 }
+
+// The same for a kernel without a barrier or a shuffle: the work-items one after the other on the calling thread (a thread per work-item
+// is too slow for launches of 10^4 - 10^5 items).  A kernel that does synchronise dereferences the null block_barrier at once.
+template <typename F>
+inline void glp_emu_launch_seq(uint64_t grid, unsigned block, F body) {
+    gridDim.x = (unsigned)grid; blockDim.x = block;
+    for (unsigned b = 0; b < grid; b++)
+        for (unsigned t = 0; t < block; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
+}
+
+// The emulated form of the drivers' launcher (GlpLaunch, csrc/glp_ctx.h): the launch sequences written beside the kernels run through it
+// unchanged, on host pointers.  n counts the launches.
+struct GlpEmuLaunch {
+    uint32_t n = 0;
+    template <class K, class... A> void launch(K kernel, uint64_t grid, unsigned block, const A&... args) {
+        glp_emu_launch_seq(grid, block, [&] { kernel(args...); });
+        n++;
+    }
+    template <class K, class... A> void launch_sync(K kernel, uint64_t grid, unsigned block, const A&... args) {
+        glp_emu_launch((unsigned)grid, block, 0, [&] { kernel(args...); });
+        n++;
+    }
+};

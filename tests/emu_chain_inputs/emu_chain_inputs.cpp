@@ -1,8 +1,8 @@
 // tests/emu_chain_inputs/emu_chain_inputs.cpp — TEST INFRASTRUCTURE.  The kernels of glp_tm_merkle_root_batch (csrc/tm_batch_kernels.cuh) and
-// of glp_header_chain_leaf_inputs (csrc/chain_inputs.cuh) on the CPU, unchanged, with the grids the driver uses (csrc/hash.hip): the leaf-hash
-// kernel (256 lanes, ceil(leaves / 256) workgroups), the fold kernel (one workgroup per tree, 64 lanes when no tree has more than 128 leaves,
-// 256 otherwise; real threads and barriers through ../emu/hip_emu.h), the check kernel (256 lanes) and the rows kernel (one 64-lane workgroup
-// per header).  The kernels without a barrier run their work-items one after the other.  The host forms are exported beside them.  Never part
+// of glp_header_chain_leaf_inputs (csrc/chain_inputs.cuh) on the CPU, unchanged, through the launch sequences the driver (csrc/tm.hip) runs
+// (glp_tm_batch_launches, glp_header_chain_launches of those headers), issued by GlpEmuLaunch of ../emu/hip_emu.h: the fold kernel with real
+// threads and barriers, the kernels without a barrier with their work-items one after the other.  This file only sets up buffers and fills
+// the argument structs with host pointers.  The host forms are exported beside them.  Never part
 // of the product.  With -DGLP_EMU_CHAIN_INPUTS_MAIN the file is a stand-alone program (built with -fsanitize=address,undefined:
 // `make sanitized`) that runs a corpus of trees and chains through both forms, every buffer a heap block of exactly its length, against a
 // separate byte-wise SHA-256 and a recursive tree.
@@ -10,38 +10,19 @@
 #include <vector>
 #include "../../0-kno-blobstreamx_amd/csrc/chain_inputs.cuh"
 
-namespace {
-template <typename F>
-void launch_seq(u64 grid, unsigned block, F body) {
-    gridDim.x = (unsigned)grid; blockDim.x = block;
-    for (unsigned b = 0; b < grid; b++)
-        for (unsigned t = 0; t < block; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
-// the two launches of tm_batch_launch (hash.hip)
-void launch_trees(GlpTmBatchArgs& a, u64 max_tree, std::vector<u32>& nodes) {
-    nodes.assign((size_t)a.total_leaves * 8, 0);                   // exact size: ASan sees any overrun
-    a.nodes = nodes.data();
-    if (a.total_leaves) launch_seq((a.total_leaves + 255) / 256, 256, [&] { glp_tm_batch_leaf_kernel<0>(a); });
-    if (max_tree <= 2 * GLP_TM_BATCH_LANES_SMALL)
-        glp_emu_launch((unsigned)a.n_trees, GLP_TM_BATCH_LANES_SMALL, 0, [&] { glp_tm_batch_fold_kernel<GLP_TM_BATCH_LANES_SMALL>(a); });
-    else
-        glp_emu_launch((unsigned)a.n_trees, GLP_TM_BATCH_LANES, 0, [&] { glp_tm_batch_fold_kernel<GLP_TM_BATCH_LANES>(a); });
-}
-}  // namespace
-
 // glp_tm_merkle_root_batch: 0, -1 (GLP_E_INVALID) or -5 (GLP_E_UNSUPPORTED); nothing is written on a refusal
 extern "C" int emu_tm_root_batch(const uint8_t* data, u64 data_len, const u64* offs, const u64* tree_first, u64 total, u64 n_trees, const u32* k256,
                                  uint8_t* roots) {
     if (n_trees == 0) return 0;
     const int bad = glp_tm_batch_check(offs, tree_first, total, n_trees, data_len);
     if (bad) return bad == 1 ? -1 : -5;
-    u64 max_tree = 0;
-    for (u64 t = 0; t < n_trees; t++) max_tree = tree_first[t + 1] - tree_first[t] > max_tree ? tree_first[t + 1] - tree_first[t] : max_tree;
+    std::vector<u32> nodes((size_t)total * 8);                      // exact size: ASan sees any overrun
     GlpTmBatchArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.data = data; a.leaf_off = offs; a.tree_first = tree_first; a.n_trees = n_trees; a.total_leaves = total; a.roots = roots; a.k256 = k256;
-    std::vector<u32> nodes;
-    launch_trees(a, max_tree, nodes);
+    a.data = data; a.leaf_off = offs; a.tree_first = tree_first; a.n_trees = n_trees; a.total_leaves = total; a.nodes = nodes.data(); a.roots = roots;
+    a.k256 = k256;
+    GlpEmuLaunch l;
+    glp_tm_batch_launches(l, a, glp_tm_batch_max_tree(tree_first, n_trees));
     return 0;
 }
 
@@ -64,7 +45,7 @@ extern "C" u64 emu_chain_input_words(const u32* field_len, u32 leaf_headers, u32
     return per ? GLP_CHAIN_ROW_HEAD + per * leaf_headers : 0;
 }
 
-// the four launches of glp_header_chain_leaf_inputs: out [n / leaf_headers][out_stride], hashes [n + 1][32], status [n]
+// the launches of glp_header_chain_leaf_inputs: out [n / leaf_headers][out_stride], hashes [n + 1][32], status [n]
 extern "C" int emu_chain_inputs(const u32* field_len, u32 leaf_headers, u32 n_groups, const uint8_t* headers, const uint8_t* start32, u64 first_height,
                                 u64 n, const u32* k256, u64* out, u64 out_stride, uint8_t* hashes, int32_t* status) {
     const u64 width = emu_chain_input_words(field_len, leaf_headers, n_groups);
@@ -73,12 +54,11 @@ extern "C" int emu_chain_inputs(const u32* field_len, u32 leaf_headers, u32 n_gr
     GlpChainArgs a;
     GlpTmBatchArgs t;
     std::memset(&t, 0, sizeof(t));
+    std::vector<u32> nodes((size_t)n * GLP_CHAIN_FIELDS * 8);       // exact size: ASan sees any overrun
     if (glp_header_chain_fill_args(a, t, field_len, leaf_headers, n_groups, headers, start32, first_height, n, out, out_stride, hashes, status,
-                                   nullptr, k256)) return -1;
-    std::vector<u32> nodes;
-    launch_trees(t, GLP_CHAIN_FIELDS, nodes);
-    launch_seq((n + 255) / 256, 256, [&] { glp_header_chain_check_kernel<0>(a); });
-    launch_seq(n, 64, [&] { glp_header_chain_rows_kernel<0>(a); });
+                                   nodes.data(), k256)) return -1;
+    GlpEmuLaunch l;
+    glp_header_chain_launches(l, a, t);
     return 0;
 }
 

@@ -16,12 +16,6 @@ void launch_2d(unsigned gx, unsigned gy, F body) {
     gridDim.y = gy;
     for (unsigned y = 0; y < gy; y++) glp_emu_launch(gx, GLP_CHECK_BLOCK, 0, [&] { blockIdx.y = y; body(); });
 }
-template <typename F>
-void launch_seq(unsigned grid, unsigned block, F body) {        // kernels without barriers: the work-items one after the other
-    gridDim.x = grid; blockDim.x = block;
-    for (unsigned b = 0; b < grid; b++)
-        for (unsigned t = 0; t < block; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
 struct SigmaHost {
     std::vector<u64> kn, kinv, wlo, whi, ilo, ihi;
     GlpSigmaTables T;
@@ -54,8 +48,8 @@ extern "C" int emu_sigma_decode(const u64* sigma_vals, u32 log_n, u32 R, u32* id
     da.sigma_vals = sigma_vals; da.ks = ks.data(); da.w_lo = S.wlo.data(); da.w_hi = log_n > GLP_CHECK_TW_SPLIT ? S.whi.data() : nullptr;
     da.T = S.T; da.idx = idx; da.hits = hits.data(); da.status = status;
     const unsigned blocks = (unsigned)((cells + 255) / 256);
-    launch_seq(blocks, 256, [&] { glp_sigma_decode_kernel<0>(da); });
-    launch_seq(blocks, 256, [&] { glp_sigma_bijective_kernel<0>(hits.data(), cells, status); });
+    glp_emu_launch_seq(blocks, 256, [&] { glp_sigma_decode_kernel<0>(da); });
+    glp_emu_launch_seq(blocks, 256, [&] { glp_sigma_bijective_kernel<0>(hits.data(), cells, status); });
     return 0;
 }
 

@@ -1,6 +1,7 @@
 // tests/emu_ed25519_inputs/emu_ed25519_inputs.cpp — TEST INFRASTRUCTURE.  The kernels of glp_ed25519_leaf_inputs and glp_ed25519_half_scalars
-// (csrc/ed25519_inputs.cuh) on the CPU, unchanged, with the grids the driver uses (64 lanes, ceil(n / 64) workgroups): the witness kernel over
-// the slots' own triples, then the input kernel.  Neither kernel has a barrier, so the work-items run one after the other.  Never part of the
+// (csrc/ed25519_inputs.cuh) on the CPU, unchanged, through the launch sequences the driver (csrc/tm.hip) runs (glp_ed25519_leaf_inputs_launches,
+// glp_ed25519_half_scalars_launch of that header), issued by GlpEmuLaunch of ../emu/hip_emu.h: the witness kernel over the slots' own triples,
+// then the input kernel.  Neither kernel has a barrier, so the work-items run one after the other.  Never part of the
 // product.  With -DGLP_EMU_ED_INPUTS_MAIN the file is a stand-alone program (built with -fsanitize=address,undefined: `make sanitized`) that runs
 // the reduction and both divisions over edge values and a few thousand random ones and checks their defining identities with a separate
 // base-2^32 big-integer reference.
@@ -8,20 +9,11 @@
 #include <vector>
 #include "../../0-kno-blobstreamx_amd/csrc/ed25519_inputs.cuh"
 
-namespace {
-template <typename F>
-void launch_seq(u64 n, F body) {
-    const unsigned grid = (unsigned)((n + 63) / 64);
-    gridDim.x = grid; blockDim.x = 64;
-    for (unsigned b = 0; b < grid; b++)
-        for (unsigned t = 0; t < 64; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
-}  // namespace
-
 extern "C" u64 emu_leaf_input_words(u32 form, u32 lo, u32 hi, u32 split) { return glp_ed25519_input_words(form, lo, hi, split); }
 
 extern "C" int emu_half_scalars(const u64* ks, u64 n, u64* out) {
-    launch_seq(n, [&] { glp_ed25519_half_scalars_kernel<0>(ks, n, out); });
+    GlpEmuLaunch l;
+    glp_ed25519_half_scalars_launch(l, ks, n, out);
     return 0;
 }
 
@@ -37,19 +29,19 @@ extern "C" int emu_divmod_l(const u64* x, u64* q, u64* r) {
 }
 
 #ifndef GLP_EMU_ED_INPUTS_MAIN      // the stand-alone program runs the reduction and the divisions only: it does not instantiate the two big kernels
-// the two launches of glp_ed25519_leaf_inputs: out [n][out_stride], status [n]
+// the launches of glp_ed25519_leaf_inputs: out [n][out_stride], status [n]
 extern "C" int emu_leaf_inputs(u32 form, u32 lo, u32 hi, u32 split, const uint8_t* pubs, const uint8_t* sigs, const uint8_t* msgs, u32 msg_stride,
                                const u32* lens, const uint8_t* flags, const uint8_t* dummy, u64 n, const u64* k512, u64* out, u64 out_stride,
                                int32_t* status) {
     const u64 width = glp_ed25519_input_words(form, lo, hi, split);
     if (!width || out_stride < width || !msg_stride) return -1;
     std::vector<u64> recs((size_t)n * GLP_ED_REC);              // exact size: ASan sees any overrun
-    launch_seq(n, [&] { glp_ed25519_witness_kernel<0>(pubs, sigs, msgs, msg_stride, lens, n, k512, recs.data()); });
     GlpEdInputsArgs a;
     a.pubs = pubs; a.sigs = sigs; a.msgs = msgs; a.lens = lens; a.flags = flags; a.dummy = dummy; a.recs = recs.data(); a.k512 = k512;
     a.out = out; a.status = status; a.n = n; a.out_stride = out_stride; a.msg_stride = msg_stride; a.form = form; a.lo = lo; a.hi = hi;
     a.split = split;
-    launch_seq(n, [&] { glp_ed25519_leaf_inputs_kernel<0>(a); });
+    GlpEmuLaunch l;
+    glp_ed25519_leaf_inputs_launches(l, a, recs.data());
     return 0;
 }
 #endif

@@ -2,7 +2,7 @@
 // CPU, unchanged, with the grids the driver uses (witness.hip), beside the single-instance bodies they must equal word for word:
 // glp_witness_place_kernel (glp_gather_u64) and glp_poseidon_gate_fill_kernel<0> / <1> / glp_sha_gate_fill_kernel (csrc/plonk_kernels.cuh).
 // Never part of the product.  None of these kernels has a barrier or a shuffle, so the work-items of a launch run one after the other on the
-// calling thread (launch_seq below) instead of one std::thread each: a 2^9 x 144 placement is 73 728 work-items per launch.
+// calling thread (glp_emu_launch_seq) instead of one std::thread each: a 2^9 x 144 placement is 73 728 work-items per launch.
 // With -DGLP_EMU_PLACE_BATCH_MAIN the file is a stand-alone program (built with -fsanitize=address,undefined: `make sanitized`) that compares
 // batched against single on small shapes.
 #include "../emu/hip_emu.h"
@@ -10,12 +10,6 @@
 #include "../../0-kno-blobstreamx_amd/csrc/place_batch_kernels.cuh"
 
 namespace {
-template <typename F>
-void launch_seq(unsigned grid, unsigned block, F body) {
-    gridDim.x = grid; blockDim.x = block;
-    for (unsigned b = 0; b < grid; b++)
-        for (unsigned t = 0; t < block; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
 unsigned capped(u64 items, unsigned per_block, unsigned cap) {
     const u64 want = (items + per_block - 1) / per_block;
     return (unsigned)(want < cap ? want : cap);
@@ -24,15 +18,15 @@ unsigned capped(u64 items, unsigned per_block, unsigned cap) {
 
 // ---- placement: the driver's grids (256 lanes, min(ceil(cells / 256), 4096) workgroups, both entry points) --------------------------------
 extern "C" int emu_place_batch(u64* dst, u64 wire_stride, const u64* src, u64 value_stride, const u32* slab_row, u32 B, const u32* index, u64 n_cells) {
-    launch_seq(capped(n_cells, 256, 4096), 256, [&] { glp_witness_place_batch_kernel<0>(dst, wire_stride, src, value_stride, slab_row, B, index, n_cells); });
+    glp_emu_launch_seq(capped(n_cells, 256, 4096), 256, [&] { glp_witness_place_batch_kernel<0>(dst, wire_stride, src, value_stride, slab_row, B, index, n_cells); });
     return 0;
 }
 extern "C" int emu_place_single(u64* dst, const u64* src, u64 n_src, const u32* index, u64 n_cells, u32* bad) {
-    launch_seq(capped(n_cells, 256, 4096), 256, [&] { glp_witness_place_kernel<0>(dst, src, n_src, index, n_cells, bad); });
+    glp_emu_launch_seq(capped(n_cells, 256, 4096), 256, [&] { glp_witness_place_kernel<0>(dst, src, n_src, index, n_cells, bad); });
     return 0;
 }
 extern "C" int emu_public_batch(u64* out, const u64* src, u64 value_stride, const u32* slab_row, u32 B, const u32* public_vars, u32 n_public) {
-    launch_seq(capped((u64)B * n_public, 256, 4096), 256, [&] { glp_witness_public_batch_kernel<0>(out, src, value_stride, slab_row, B, public_vars, n_public); });
+    glp_emu_launch_seq(capped((u64)B * n_public, 256, 4096), 256, [&] { glp_witness_public_batch_kernel<0>(out, src, value_stride, slab_row, B, public_vars, n_public); });
     return 0;
 }
 
@@ -40,23 +34,23 @@ extern "C" int emu_public_batch(u64* out, const u64* src, u64 value_stride, cons
 extern "C" int emu_pos_fill_batch(u64* wires, u64 wire_stride, u32 log_n, const u32* rows, u32 n_rows, u32 B, const u64* consts, int small_mds) {
     const u32 bpi = (n_rows + 63) / 64;
     const u64 n = 1ull << log_n;
-    if (small_mds) launch_seq(B * bpi, 64, [&] { glp_poseidon_gate_fill_batch_kernel<1>(wires, wire_stride, n, rows, n_rows, bpi, consts); });
-    else launch_seq(B * bpi, 64, [&] { glp_poseidon_gate_fill_batch_kernel<0>(wires, wire_stride, n, rows, n_rows, bpi, consts); });
+    if (small_mds) glp_emu_launch_seq(B * bpi, 64, [&] { glp_poseidon_gate_fill_batch_kernel<1>(wires, wire_stride, n, rows, n_rows, bpi, consts); });
+    else glp_emu_launch_seq(B * bpi, 64, [&] { glp_poseidon_gate_fill_batch_kernel<0>(wires, wire_stride, n, rows, n_rows, bpi, consts); });
     return 0;
 }
 extern "C" int emu_pos_fill_single(u64* wires, u32 log_n, const u32* rows, u32 n_rows, const u64* consts, int small_mds) {
     const u64 n = 1ull << log_n;
-    if (small_mds) launch_seq((n_rows + 63) / 64, 64, [&] { glp_poseidon_gate_fill_kernel<1>(wires, n, rows, n_rows, consts); });
-    else launch_seq((n_rows + 63) / 64, 64, [&] { glp_poseidon_gate_fill_kernel<0>(wires, n, rows, n_rows, consts); });
+    if (small_mds) glp_emu_launch_seq((n_rows + 63) / 64, 64, [&] { glp_poseidon_gate_fill_kernel<1>(wires, n, rows, n_rows, consts); });
+    else glp_emu_launch_seq((n_rows + 63) / 64, 64, [&] { glp_poseidon_gate_fill_kernel<0>(wires, n, rows, n_rows, consts); });
     return 0;
 }
 extern "C" int emu_sha_fill_batch(u64* wires, u64 wire_stride, u32 log_n, const u32* rows, const u32* kinds, u32 n_rows, u32 B) {
     const u32 bpi = (n_rows + 63) / 64;
-    launch_seq(B * bpi, 64, [&] { glp_sha_gate_fill_batch_kernel<0>(wires, wire_stride, 1ull << log_n, rows, kinds, n_rows, bpi); });
+    glp_emu_launch_seq(B * bpi, 64, [&] { glp_sha_gate_fill_batch_kernel<0>(wires, wire_stride, 1ull << log_n, rows, kinds, n_rows, bpi); });
     return 0;
 }
 extern "C" int emu_sha_fill_single(u64* wires, u32 log_n, const u32* rows, const u32* kinds, u32 n_rows) {
-    launch_seq((n_rows + 63) / 64, 64, [&] { glp_sha_gate_fill_kernel<0>(wires, 1ull << log_n, rows, kinds, n_rows); });
+    glp_emu_launch_seq((n_rows + 63) / 64, 64, [&] { glp_sha_gate_fill_kernel<0>(wires, 1ull << log_n, rows, kinds, n_rows); });
     return 0;
 }
 

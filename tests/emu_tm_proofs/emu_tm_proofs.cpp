@@ -1,23 +1,14 @@
 // tests/emu_tm_proofs/emu_tm_proofs.cpp — TEST INFRASTRUCTURE.  The kernels of glp_tm_forest_create, glp_tm_forest_proofs and
-// glp_tm_verify_inclusion_batch (csrc/tm_proof_kernels.cuh) on the CPU, unchanged, with the checks, the plan and the grids the driver uses
-// (csrc/hash.hip): the leaf-hash kernel (256 lanes), one level kernel per level while the widest tree has more than 512 nodes (256 lanes, one
-// work-item per output node), the top kernel (one workgroup per tree, 64 lanes when no tree has more than 128 nodes there, 256 otherwise; real
-// threads and barriers through ../emu/hip_emu.h), the path kernel and the verify kernel (256 lanes).  The kernels without a barrier run their
-// work-items one after the other.  The host forms are exported beside them.  Never part of the product.  With -DGLP_EMU_TM_PROOFS_MAIN the
+// glp_tm_verify_inclusion_batch (csrc/tm_proof_kernels.cuh) on the CPU, unchanged, with the checks and the plan the driver uses (csrc/tm.hip)
+// and through the driver's own launch sequences (glp_tm_forest_create_launches, glp_tm_path_launch, glp_tm_verify_launch of that header),
+// issued by GlpEmuLaunch of ../emu/hip_emu.h: the top kernel with real threads and barriers, the kernels without a barrier with their
+// work-items one after the other.  This file only sets up buffers and fills the argument structs with host pointers.
+// The host forms are exported beside them.  Never part of the product.  With -DGLP_EMU_TM_PROOFS_MAIN the
 // file is a stand-alone program (built with -fsanitize=address,undefined: `make sanitized`) that runs a corpus of forests, paths and tampered
 // proofs through both forms, every buffer a heap block of exactly its length, against a separate byte-wise SHA-256 and the RECURSIVE tree.
 #include "../emu/hip_emu.h"
 #include <vector>
 #include "../../0-kno-blobstreamx_amd/csrc/tm_proof_kernels.cuh"
-
-namespace {
-template <typename F>
-void launch_seq(u64 grid, unsigned block, F body) {
-    gridDim.x = (unsigned)grid; blockDim.x = block;
-    for (unsigned b = 0; b < grid; b++)
-        for (unsigned t = 0; t < block; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
-}  // namespace
 
 // glp_tm_forest_create + glp_tm_forest_proofs: 0, -1 (GLP_E_INVALID) or -5 (GLP_E_UNSUPPORTED); nothing is written on a refusal.  roots may be
 // NULL; launches[0] = launches of create, launches[1] = of proofs (may be NULL)
@@ -34,41 +25,21 @@ extern "C" int emu_tm_forest_proofs(const uint8_t* data, u64 data_len, const u64
     std::vector<u32> slab((size_t)plan.total_nodes * 8);                // exact size: ASan sees any overrun
     std::vector<uint8_t> own_roots;
     if (!roots) { own_roots.resize((size_t)n_trees * 32); roots = own_roots.data(); }
-    u32 n_launch = 0;
     GlpTmForestArgs a;
     std::memset(&a, 0, sizeof(a));
     a.tree_first = tree_first; a.upper_base = plan.upper_base.data(); a.n_trees = n_trees; a.total_leaves = total; a.slab = slab.data();
     a.roots = roots; a.k256 = k256;
-    if (total) {
-        GlpTmBatchArgs b;
-        std::memset(&b, 0, sizeof(b));
-        b.data = data; b.leaf_off = offs; b.tree_first = tree_first; b.n_trees = n_trees; b.total_leaves = total; b.nodes = slab.data();
-        b.roots = roots; b.k256 = k256;
-        launch_seq((total + 255) / 256, 256, [&] { glp_tm_batch_leaf_kernel<0>(b); });
-        n_launch++;
-    }
-    for (size_t l = 0; l < plan.level_pre.size(); l++) {
-        a.level = (u32)l;
-        a.level_pre = plan.level_pre[l].data();
-        launch_seq((plan.level_pre[l][n_trees] + 255) / 256, 256, [&] { glp_tm_forest_level_kernel<0>(a); });
-        n_launch++;
-    }
-    a.level = plan.top_level;
-    a.level_pre = nullptr;
-    if (plan.top_width <= 2 * GLP_TM_BATCH_LANES_SMALL)
-        glp_emu_launch((unsigned)n_trees, GLP_TM_BATCH_LANES_SMALL, 0, [&] { glp_tm_forest_top_kernel<GLP_TM_BATCH_LANES_SMALL>(a); });
-    else
-        glp_emu_launch((unsigned)n_trees, GLP_TM_BATCH_LANES, 0, [&] { glp_tm_forest_top_kernel<GLP_TM_BATCH_LANES>(a); });
-    n_launch++;
-    if (launches) launches[0] = n_launch;
+    GlpEmuLaunch create, proofs;
+    glp_tm_forest_create_launches(create, a, glp_tm_forest_leaf_args(a, data, offs), plan, [&](size_t l) { return plan.level_pre[l].data(); });
+    if (launches) launches[0] = create.n;
     if (n_queries == 0) return 0;
     GlpTmPathArgs p;
     std::memset(&p, 0, sizeof(p));
     p.f = a;
     p.query_tree = query_tree; p.query_leaf = query_leaf; p.n_queries = n_queries; p.aunts = aunts; p.n_aunts = n_aunts; p.leaf_hash = leaf_hashes;
     p.aunt_stride = aunt_stride;
-    launch_seq((n_queries + 255) / 256, 256, [&] { glp_tm_path_kernel<0>(p); });
-    if (launches) launches[1] = 1;
+    glp_tm_path_launch(proofs, p);
+    if (launches) launches[1] = proofs.n;
     return 0;
 }
 
@@ -91,7 +62,8 @@ extern "C" int emu_tm_verify(const uint8_t* roots, u64 n_roots, const u32* root_
     std::memset(&a, 0, sizeof(a));
     a.roots = roots; a.root_of = root_of; a.data = data; a.leaf_off = offs; a.index = index; a.total = total; a.aunts = aunts; a.n_aunts = n_aunts;
     a.n = n; a.status = status; a.k256 = k256; a.aunt_stride = aunt_stride;
-    launch_seq((n + 255) / 256, 256, [&] { glp_tm_verify_kernel<0>(a); });
+    GlpEmuLaunch l;
+    glp_tm_verify_launch(l, a);
     return 0;
 }
 

@@ -14,13 +14,6 @@
 using namespace glp_verify;
 
 namespace {
-template <typename F>
-void launch_seq(unsigned grid, unsigned block, F body) {        // kernels without barriers: the work-items one after the other
-    gridDim.x = grid; blockDim.x = block;
-    for (unsigned b = 0; b < grid; b++)
-        for (unsigned t = 0; t < block; t++) { blockIdx.x = b; threadIdx.x = t; body(); }
-}
-
 // csrc/verify.hip::device_phase with the copies replaced by one exact-size heap block
 void emu_device_phase(const VerifyPlan& P, const std::vector<const u64*>& words, const Hasher& h, std::vector<unsigned long long>& keys, u32* counts) {
     const size_t nd = P.desc.size();
@@ -54,12 +47,12 @@ void emu_device_phase(const VerifyPlan& P, const std::vector<const u64*>& words,
     a.k = h.k();
     if (n_merkle) {
         const unsigned g = (unsigned)((n_merkle + GLP_VB_BLOCK - 1) / GLP_VB_BLOCK);
-        if (h.small_mds) launch_seq(g, GLP_VB_BLOCK, [&] { glp_verify_merkle_kernel<true>(a); });
-        else launch_seq(g, GLP_VB_BLOCK, [&] { glp_verify_merkle_kernel<false>(a); });
+        if (h.small_mds) glp_emu_launch_seq(g, GLP_VB_BLOCK, [&] { glp_verify_merkle_kernel<true>(a); });
+        else glp_emu_launch_seq(g, GLP_VB_BLOCK, [&] { glp_verify_merkle_kernel<false>(a); });
         counts[0]++;
     }
     a.items = up.get() + o_items + n_merkle; a.n_items = n_arith;
-    launch_seq((unsigned)((n_arith + GLP_VB_BLOCK - 1) / GLP_VB_BLOCK), GLP_VB_BLOCK, [&] { glp_verify_arith_kernel<0>(a); });
+    glp_emu_launch_seq((unsigned)((n_arith + GLP_VB_BLOCK - 1) / GLP_VB_BLOCK), GLP_VB_BLOCK, [&] { glp_verify_arith_kernel<0>(a); });
     counts[0]++;
     for (size_t k = 0; k < nd; k++) keys[k] = a.keys[k];
     counts[1]++;
